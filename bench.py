@@ -4,9 +4,14 @@
     python bench.py --gpus N --steps K --warmup W            (N > 1: this process only launches the N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --workload cifar20-pruned | sd256 | sd512 | celeba | celeba-pruned [--precision bf16]   (one labelled line)
-With no --workload the line is the headline (cifar20) and, at N = 1, carries the other workloads of the path as
+    python bench.py ... --dump-outputs DIR      (also writes what the last timed step computed as DIR/<name>.npy)
+A plain run does only what its headline figure needs: set up, W warm-up steps, K timed steps with no per-launch brackets,
+one short JSON line.  `--full` adds everything else: HIP-event brackets around every contraction launch of the timed region
+(`roofline`, `contraction_kernels`; the launch-bound SD bf16 step brackets a second pass of the same K steps instead, and the
+CIFAR `one_stream_*` keys come from one more pass), the separate U-Net training rate, the CPU baseline and - with no
+--workload at N = 1 - the other workloads of the path as
 `"secondary": {"cifar20-pruned": {...}, "sd512": {...}, "celeba": {...}, "celeba-pruned": {...}}`, each timed the same way
-(barrier-bracketed, HIP-event kernel brackets) with its own `roofline`; `--no-secondary` skips them.
+with its own `roofline`; `--no-secondary`, `--no-cpu-baseline`, ... drop single parts of it.
 
 Workload (config.workload): one coalition of the reference's CIFAR-20 configuration =
 gd_steps=1000 fine-tuning steps at B=128 (noise, antithetic t, add_noise, U-Net fwd, MSE, bwd,
@@ -41,6 +46,8 @@ UNET_GFLOP_PER_IMG = 12.44          # forward, SURVEY §8d (6.222 GMAC)
 BF16_MFMA_PEAK_TF = 2500.0          # dense bf16 MFMA (v_mfma_f32_32x32x16_bf16)
 F32_MFMA_PEAK_TF = 157.3            # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 64 FLOP/clk/SIMD
 HBM_PEAK_GBPS = 8000.0              # MI355X_MICROARCH.md: HBM3E spec peak (6.29 TB/s measured with a float4 copy)
+DUMP_MAX_ELEMS = 1 << 22            # --dump-outputs: per array (16 MB in float32); a workload writes at most four arrays
+DUMP_MAX_BYTES = 64 << 20
 
 
 PRUNED_WIDTHS = (96, 192, 192, 192)      # magnitude pruning at ratio 0.3 keeps 32-channel GroupNorm groups whole
@@ -98,9 +105,17 @@ def parse():
     ap.add_argument("--stub", action="store_true",
                     help="CPU rehearsal of the launcher / process group / final all_gather with a stub engine over gloo "
                          "(tests only: the line is marked \"stub\": true and is not a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: kernel brackets / roofline, the U-Net training rate, "
+                         "the CPU baseline and the secondary workloads (off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64; arrays over "
+                         f"{DUMP_MAX_ELEMS} elements as a fixed seeded sample of that many)")
     a = ap.parse_args()
     if a.widths == "pruned":
         a.workload = "cifar20-pruned"
+    if not a.full:                                  # a plain run: the headline figure and nothing else
+        a.no_kernel_timing = a.no_train_rate = a.no_cpu_baseline = a.no_one_stream_pass = a.no_secondary = True
     a.secondary = a.workload is None and not a.no_secondary and not a.full_coalition and not a.stub
     a.workload = a.workload or "cifar20"
     return a
@@ -264,6 +279,39 @@ class SDRunner:
         noise = torch.randn_like(x0)
         ts = torch.randint(0, 1000, (self.batch,), device=self.dev).long()
         return self.trainer.step(x0, noise, ts, self.text.index_select(0, sel))
+
+
+def step_outputs(run, loss):
+    """What the last timed step handed back to its caller: the training step's loss, the trained parameters and (where the
+    workload keeps one) their EMA in the models' own layout, and for a CIFAR slice the sampler's DDIM state after its step."""
+    tr = run.trainer
+    out = {"train_loss": loss.reshape(1), "params": torch.cat([p.detach().reshape(-1) for p in tr.params])}
+    if tr.ema is not None:
+        out["ema_params"] = torch.cat([s.reshape(-1) for s in tr.ema.shadow_params])
+    if isinstance(run, SliceRunner):
+        out["sampler_x"] = run.x
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor as <path>/<name>.npy, float64 kept, any other dtype as float32.  A tensor of more than
+    DUMP_MAX_ELEMS elements is written as its elements at a fixed, seeded set of flat positions (the same set in every run)."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        host[name] = t.cpu().numpy()
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(path, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    log(f"outputs of the last timed step -> {path}: " + ", ".join(f"{k} {list(v.shape)}" for k, v in host.items()))
 
 
 def _threads():
@@ -584,6 +632,10 @@ def measure(a, name, steps, warmup, env, headline):
         barrier()
         dt = time.time() - t0
         units = steps * world                                           # coalitions
+        if a.dump_outputs and headline and rank == 0:
+            r = recs[-1]
+            dump_outputs(a.dump_outputs, {"coalition_scores": torch.tensor(
+                [r.fid_value, r.loss_last, r.inception_score, r.precision, r.recall], dtype=torch.float64)})
     else:
         if wl["kind"] == "cifar":
             run = SliceRunner(engine, removal_seed=rank, in_flight=a.in_flight)
@@ -612,6 +664,8 @@ def measure(a, name, steps, warmup, env, headline):
         dt = time.time() - t0
         log(f"timed region done: {dt:.2f}s for {steps} steps")
         ops.PROFILER = None
+        if a.dump_outputs and headline and rank == 0:                  # before any further pass moves the state on
+            dump_outputs(a.dump_outputs, step_outputs(run, loss))
         if separate_pass:
             graphed, run.trainer.use_graph = run.trainer.use_graph, False          # the brackets need eager launches
             prof = ops.GemmProfiler()

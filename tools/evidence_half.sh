@@ -6,8 +6,8 @@ TAG=${1:-r04}
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
-python3 bench.py --workload sd512 --precision bf16 --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_sd512_bf16.json 2> $O/${TAG}_bench_sd512_bf16.err
-python3 bench.py --workload sd256 --precision bf16 --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_sd256_bf16.json 2> $O/${TAG}_bench_sd256_bf16.err
+python3 bench.py --full --workload sd512 --precision bf16 --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_sd512_bf16.json 2> $O/${TAG}_bench_sd512_bf16.err
+python3 bench.py --full --workload sd256 --precision bf16 --steps 10 --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_sd256_bf16.json 2> $O/${TAG}_bench_sd256_bf16.err
 echo "bench lines done"
 rm -rf $O/prof_h
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_h -- python3 bench.py --workload sd512 --precision bf16 --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-timing > $O/${TAG}_bench_sd512_bf16_under_rocprof.json 2> $O/${TAG}_prof_sd512_bf16.err

@@ -1,6 +1,6 @@
 # Everything profiles/<tag>_* is made from, in one GPU-box call:  bash tools/evidence_round.sh r03
-#   <tag>_bench_default.json                 python bench.py (headline + secondary workloads + cpu_baseline)
-#   <tag>_bench_<workload>_kernel_stats.csv  rocprofv3 --kernel-trace --stats of python bench.py --workload W  (+ _under_rocprof.json)
+#   <tag>_bench_default.json                 python bench.py --full (headline + secondary workloads + cpu_baseline)
+#   <tag>_bench_<workload>_kernel_stats.csv  rocprofv3 --kernel-trace --stats of python bench.py --full --workload W  (+ _under_rocprof.json)
 #   <tag>_pmc_{FETCH,WRITE}_SIZE_w{32,16}.json  separate --pmc passes over the cifar20 launch mix
 #   <tag>_train_step_kernel_stats.csv        rocprofv3 of tools/prof_train.py
 #   <tag>_bench_bf16_<workload>.json         bf16-operand mode lines (not the headline)
@@ -16,7 +16,7 @@ O=$R/gpurun_out
 export TMPDIR=/tmp
 cd $R
 if [[ $HALF == *a* ]]; then
-python3 bench.py > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
+python3 bench.py --full > $O/${TAG}_bench_default.json 2> $O/${TAG}_bench_default.err
 echo "done default bench"
 bash tools/prof_round.sh $TAG "cifar20 cifar20-pruned sd256 sd512 celeba celeba-pruned" pmc
 fi
@@ -27,7 +27,7 @@ python3 tools/summarize_rocprof.py $(find $O/prof_train -name "*kernel_stats.csv
 rm -rf $O/prof_train
 for wl in cifar20 sd256 sd512; do
   st=20; [ $wl != cifar20 ] && st=5
-  timeout -k 10 200 python3 bench.py --workload $wl --precision bf16 --steps $st --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_bf16_${wl}.json 2> $O/${TAG}_bench_bf16_${wl}.err
+  timeout -k 10 200 python3 bench.py --full --workload $wl --precision bf16 --steps $st --warmup 2 --no-cpu-baseline > $O/${TAG}_bench_bf16_${wl}.json 2> $O/${TAG}_bench_bf16_${wl}.err
   echo "done bf16 $wl"
 done
 timeout -k 10 300 python3 tools/ab_winograd.py > $O/${TAG}_ab_winograd.txt 2>&1

@@ -10,12 +10,12 @@ for wl in $WLS; do
   steps=20; case $wl in sd256|sd512|celeba|celeba-pruned) steps=5;; esac
   rm -rf $O/prof_$wl
   # (CIFAR workloads run two coalitions in flight on two streams: --no-one-stream-pass keeps the profile to the timed region)
-  (cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -- python3 bench.py --workload $wl --steps $steps --warmup 2 --no-cpu-baseline --no-train-rate --no-one-stream-pass > $O/${TAG}_bench_${wl}_under_rocprof.json 2> $O/${TAG}_prof_bench_$wl.err)
+  (cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -- python3 bench.py --full --workload $wl --steps $steps --warmup 2 --no-cpu-baseline --no-train-rate --no-one-stream-pass > $O/${TAG}_bench_${wl}_under_rocprof.json 2> $O/${TAG}_prof_bench_$wl.err)
   f=$(find $O/prof_$wl -name "*kernel_stats.csv" | head -1)
   python3 $R/tools/summarize_rocprof.py $f $O/${TAG}_bench_${wl}_kernel_stats.csv
   rm -rf $O/prof_$wl
   case $wl in cifar20|cifar20-pruned)       # the same on ONE stream: per-kernel durations without the other stream's share of the chip
-    (cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -- python3 bench.py --workload $wl --steps $steps --warmup 2 --no-cpu-baseline --no-train-rate --in-flight 1 > $O/${TAG}_bench_${wl}_one_stream_under_rocprof.json 2> $O/${TAG}_prof_bench_${wl}_one_stream.err)
+    (cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$wl -- python3 bench.py --full --workload $wl --steps $steps --warmup 2 --no-cpu-baseline --no-train-rate --in-flight 1 > $O/${TAG}_bench_${wl}_one_stream_under_rocprof.json 2> $O/${TAG}_prof_bench_${wl}_one_stream.err)
     f=$(find $O/prof_$wl -name "*kernel_stats.csv" | head -1)
     python3 $R/tools/summarize_rocprof.py $f $O/${TAG}_bench_${wl}_one_stream_kernel_stats.csv
     rm -rf $O/prof_$wl;;
