@@ -2346,6 +2346,20 @@ static int pick_vec(const gad_gemm_args* a) {
   return vec;
 }
 
+// tile_hint values that force a route or a tile (A/B tools, tests; 0 = the planner decides): include/gad.h
+enum : int32_t {
+  HINT_128 = 1,              // engine: 128 x 128 tiles; patch weight gradient: 128-channel tiles
+  HINT_64 = 2,               // engine: 64 x 64 tiles (keeps the LDS-patch kernels out)
+  HINT_128x64 = 3,           // engine: 128 x 64 tiles (dense fp32 forms)
+  HINT_WGRAD_96 = 4, HINT_WGRAD_64 = 5, HINT_WGRAD_32 = 6,   // patch weight gradient on 96 / 64 / 32-channel tiles
+  HINT_WINO2 = 7,            // Winograd F(2x2)
+  HINT_WINO4 = 8,            // Winograd F(4x4), the planner's form; the Winograd weight gradient
+  HINT_WINO4_FUSED32 = 9,    // F(4x4) one-launch form on 32-tile blocks
+  HINT_WINO4_THREE = 10,     // F(4x4) three-launch forms
+  HINT_WINO4_FUSED64 = 11,   // F(4x4) one-launch form on 64-tile blocks
+  HINT_SPLIT_M = 1000,       // + m1: patch weight gradient as two launches, rows [0, m1) on 128-channel tiles, the rest planned
+};
+
 struct Plan {
   int bm, bn, tiles_m, tiles_n, splitk, ktiles_per_split;
   long nblocks;
@@ -2367,8 +2381,8 @@ static Plan make_plan(const gad_gemm_args* a) {
   double best = 1e30;
   Plan pl{};
   for (int bm = 128; bm >= 64; bm -= 64) {
-    if (a->tile_hint == 1 && bm != 128) continue;
-    if (a->tile_hint == 2 && bm != 64) continue;
+    if (a->tile_hint == HINT_128 && bm != 128) continue;
+    if (a->tile_hint == HINT_64 && bm != 64) continue;
     // bf16-operand kernels: 3 / 6 workgroups per CU; a K step is bound by staging (gather + convert + LDS), not by
     // the 8 / 2 MFMAs, so the per-step cost of a 64x64 tile is about a third of a 128x128 tile's, not a quarter
     const bool bf = a->operand_precision == 1 && pick_vec(a) == 4;
@@ -2427,23 +2441,17 @@ static Plan make_plan(const gad_gemm_args* a) {
   // ... and where N is a whole number of 128-wide tiles and the launch is many rounds deep, the 128 x 128 tile measured another
   // 3-9 % faster (attention projections / 1x1 shortcuts of the CIFAR sampler at B = 1024: tools/ab_dense_tiles.py,
   // profiles/r04_ab_dense_tiles.txt) - N = 320 / 640 (SD) keep 128 x 64, which pads nothing there
-  if (auto_128x64 && a->N % 128 == 0 && (long)gad_ceil_div(a->M, 128) * (a->N / 128) >= 1024) {
-    pl.bm = 128; pl.bn = 128;
+  auto whole_k = [&](int bn) {                 // 128 x bn tiles, no split
+    pl.bm = 128; pl.bn = bn;
     pl.tiles_m = (int)gad_ceil_div(a->M, 128);
-    pl.tiles_n = a->N / 128;
+    pl.tiles_n = (int)gad_ceil_div(a->N, bn);
     pl.splitk = 1;
     pl.ktiles_per_split = kt;
     pl.nblocks = (long)pl.tiles_m * pl.tiles_n * batch;
     return pl;
-  }
-  if ((a->tile_hint == 3 || auto_128x64) && dense_128x64_ok(a)) {
-    pl.bm = 128; pl.bn = 64;
-    pl.tiles_m = (int)gad_ceil_div(a->M, 128);
-    pl.tiles_n = (int)gad_ceil_div(a->N, 64);
-    pl.splitk = 1;
-    pl.ktiles_per_split = kt;
-    pl.nblocks = (long)pl.tiles_m * pl.tiles_n * batch;
-  }
+  };
+  if (auto_128x64 && a->N % 128 == 0 && (long)gad_ceil_div(a->M, 128) * (a->N / 128) >= 1024) return whole_k(128);
+  if ((a->tile_hint == HINT_128x64 || auto_128x64) && dense_128x64_ok(a)) return whole_k(64);
   return pl;
 }
 
@@ -2480,16 +2488,20 @@ static bool use_bf16(const gad_gemm_args* a) {
   return a->operand_precision == 1 && pick_vec(a) == 4;
 }
 
+// 3x3 / stride 1 / pad 1 with output maps the size of the (upsampled) input: the geometry of the patch and Winograd kernels
+static bool same_3x3(const gad_conv_geom& g) {
+  return g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad_t == 1 && g.pad_l == 1 && g.Ho == (g.upsample ? 2 * g.H : g.H) &&
+         g.Wo == (g.upsample ? 2 * g.W : g.W);
+}
+
 // 3x3 / stride 1 / pad 1 forward conv whose 128-pixel tiles are whole rows of one image: the LDS-patch kernel applies
 static bool patch_conv_geom(const gad_gemm_args* a, bool dgrad = false) {
   const gad_conv_geom& g = a->g;
   const bool modes = dgrad ? (a->a_mode == GAD_A_CONVT && a->b_mode == GAD_B_WDGRAD && !g.upsample)
                            : (a->a_mode == GAD_A_CONV && a->b_mode == GAD_B_KC);
-  return pick_vec(a) == 4 && modes && !a->A2 && g.KH == 3 && g.KW == 3 &&
-         g.stride == 1 && g.pad_t == 1 && g.pad_l == 1 && g.Ho == (g.upsample ? 2 * g.H : g.H) &&
-         g.Wo == (g.upsample ? 2 * g.W : g.W) &&
+  return pick_vec(a) == 4 && modes && !a->A2 && same_3x3(g) &&
          (((g.Wo == 64 || g.Wo == 32 || g.Wo == 16) && (g.Ho * g.Wo) % 128 == 0) ||
-          ((g.Wo == 8 || g.Wo == 4) && g.Ho == g.Wo && a->M % 128 == 0)) && g.C % BK == 0 && a->tile_hint != 2 && a->splitk_hint <= 1 &&
+          ((g.Wo == 8 || g.Wo == 4) && g.Ho == g.Wo && a->M % 128 == 0)) && g.C % BK == 0 && a->tile_hint != HINT_64 && a->splitk_hint <= 1 &&
          (a->batch <= 1) && (long)a->M * g.ldx < (1L << 31) && !(a->flags & GAD_GEMM_NO_PATCH);
 }
 static bool use_patch_conv(const gad_gemm_args* a) { return use_bf16(a) && patch_conv_geom(a); }
@@ -2578,7 +2590,7 @@ static bool patch_split_n(const gad_gemm_args* a, int* n1_out) {
 static bool use_fewout_conv(const gad_gemm_args* a) {
   const gad_conv_geom& g = a->g;
   return a->a_mode == GAD_A_CONV && a->b_mode == GAD_B_KC && a->N <= 4 && !a->A2 && !a->A_k2 && pick_vec(a) == 4 &&
-         g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad_t == 1 && g.pad_l == 1 && !g.upsample && g.Ho == g.H && g.Wo == g.W &&
+         same_3x3(g) && !g.upsample &&
          (g.W == 64 || g.W == 32 || g.W == 16) && (g.H * g.W) % 256 == 0 && a->M % 256 == 0 && g.C % BK == 0 &&
          a->batch <= 1 && !a->rowadd && !a->residual && a->tile_hint == 0 && a->splitk_hint <= 1 &&
          (long)a->M * g.ldx < (1L << 31) && !(a->flags & GAD_GEMM_NO_PATCH);
@@ -2618,14 +2630,12 @@ static int wgrad_patch_splits(const gad_gemm_args* a, int* bm_out = nullptr) {
   const gad_conv_geom& g = a->g;
   if (a->flags & GAD_GEMM_NO_PATCH) return 0;
   if (use_bf16(a) || pick_vec(a) != 4 || a->a_mode != GAD_A_MC || a->b_mode != GAD_B_CONV) return 0;
-  if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1) return 0;
-  if (g.Ho != (g.upsample ? 2 * g.H : g.H) || g.Wo != (g.upsample ? 2 * g.W : g.W)) return 0;
+  if (!same_3x3(g)) return 0;
   if (!(g.Wo == 64 || g.Wo == 32 || g.Wo == 16 || g.Wo == 8) || (g.Ho * g.Wo) % BK != 0 || a->K % BK != 0 || g.C % BK != 0 || a->M % 32 != 0) return 0;
-  if (a->batch > 1 || a->tile_hint == 2 || a->splitk_hint > 0 || a->lda % 4 != 0) return 0;
+  if (a->batch > 1 || a->tile_hint == HINT_64 || a->splitk_hint > 0 || a->lda % 4 != 0) return 0;
   if ((long)(a->K / (g.Ho * g.Wo)) * g.H * g.W * g.ldx >= (1L << 31)) return 0;
-  // tile_hint (A/B tools, tests): 1 / 4 / 5 / 6 = one launch on 128 / 96 / 64 / 32-channel tiles; >= 1000 is handled by
-  // wgrad_split_m (rows [0, hint - 1000) on 128-channel tiles, the rest planned)
-  const int bm = a->tile_hint == 1 ? 128 : a->tile_hint == 4 ? 96 : a->tile_hint == 5 ? 64 : a->tile_hint == 6 ? 32 : wgrad_patch_bm(a);
+  const int bm = a->tile_hint == HINT_128 ? 128 : a->tile_hint == HINT_WGRAD_96 ? 96 : a->tile_hint == HINT_WGRAD_64 ? 64
+               : a->tile_hint == HINT_WGRAD_32 ? 32 : wgrad_patch_bm(a);
   if (bm_out) *bm_out = bm;
   return (int)wgrad_sp(a->M, bm, g.C, a->K / BK);
 }
@@ -2634,10 +2644,10 @@ static int wgrad_patch_splits(const gad_gemm_args* a, int* bm_out = nullptr) {
 // 672 = 384 + 288 run as two launches over disjoint row ranges (128-channel tiles, then one narrower width) when the
 // launch model prefers that to the best single width by 2 % or more.
 static bool wgrad_split_m(const gad_gemm_args* a, int* m1_out) {
-  if (a->tile_hint >= 1000) {                                // forced split point (A/B tools)
+  if (a->tile_hint >= HINT_SPLIT_M) {                        // forced split point (A/B tools)
     gad_gemm_args probe = *a;
     probe.tile_hint = 0;
-    const int m1 = a->tile_hint - 1000;
+    const int m1 = a->tile_hint - HINT_SPLIT_M;
     if (m1 <= 0 || m1 >= a->M || m1 % 128 != 0 || (a->M - m1) % 32 != 0 || !wgrad_patch_splits(&probe)) return false;
     *m1_out = m1;
     return true;
@@ -2654,15 +2664,6 @@ static bool wgrad_split_m(const gad_gemm_args* a, int* m1_out) {
     if (c < best) { best = c; *m1_out = m1; found = true; }
   }
   return found;
-}
-static void wgrad_split_args(const gad_gemm_args* a, int m1, gad_gemm_args* lo, gad_gemm_args* hi) {
-  *lo = *a;
-  *hi = *a;
-  if (a->tile_hint >= 1000) lo->tile_hint = hi->tile_hint = 0;
-  lo->M = m1;
-  hi->M = a->M - m1;
-  hi->A = a->A + m1;                       // A_MC: dy [pixels][Cout], the output channel is the contiguous index
-  hi->C = a->C + (long)m1 * a->ldc;
 }
 
 // 1x1 / stride 1 / pad 0 convolutions (ResNet shortcuts, attention projections of the LDM / SD blocks written as convs) are
@@ -2691,14 +2692,15 @@ static bool as_dense_1x1(const gad_gemm_args* a, gad_gemm_args* out) {
   }
   return true;
 }
-#define GAD_CANON(a) gad_gemm_args canon_; if (as_dense_1x1((a), &canon_)) (a) = &canon_
+static gad_gemm_args canonical(const gad_gemm_args* a) {
+  gad_gemm_args c;
+  return as_dense_1x1(a, &c) ? c : *a;
+}
 
 // Winograd F(2x2, 3x3) route of the fp32 3x3 / stride 1 / pad 1 forward convolution (and, through ops.dgrad_as_forward, of
 // its data gradient): taken when the caller supplies the transformed weights (B_wino) and the launch has tiles enough to
 // fill the chip - small maps at small batch keep the direct LDS-patch kernels and their split-K.
-constexpr int GAD_GEMM_INTERNAL_WINO4 = 1 << 30;
-// (GAD_GEMM_WINO_WGRAD = 32 is public: gad.h)
-   // set by gad_gemm on its own batched sub-launch (names the kernel instance apart)
+constexpr int GAD_GEMM_INTERNAL_WINO4 = 1 << 30;   // set by gad_gemm on its own batched sub-launches (names the kernel instance apart)
 struct WinoPlan {
   int f;                     // 2: F(2x2,3x3) fused kernels; 4: F(4x4,3x3)
   int fused4;                // f = 4: 0 = 36 batched products on the generic engine + output kernel, 1 = the six-position product kernel
@@ -2711,9 +2713,8 @@ struct WinoPlan {
 static bool use_wino(const gad_gemm_args* a, WinoPlan* wp) {
   const gad_conv_geom& g = a->g;
   if ((!a->B_wino && !a->B_wino4) || a->operand_precision != 0 || a->a_mode != GAD_A_CONV || a->b_mode != GAD_B_KC || a->A2 || a->A_k2) return false;
-  const int He = g.upsample ? 2 * g.H : g.H, We = g.upsample ? 2 * g.W : g.W;
-  if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1 || g.Ho != He || g.Wo != We || (He & 1) || (We & 1)) return false;
-  if (g.C % BK != 0 || g.ldx % 4 != 0 || a->N % 4 != 0 || a->N < 64 || (a->tile_hint != 0 && a->tile_hint != 7 && a->tile_hint != 8 && a->tile_hint != 9 && a->tile_hint != 10 && a->tile_hint != 11) || a->splitk_hint > 0 || a->batch > 1) return false;
+  if (!same_3x3(g) || (g.Ho & 1) || (g.Wo & 1)) return false;
+  if (g.C % BK != 0 || g.ldx % 4 != 0 || a->N % 4 != 0 || a->N < 64 || (a->tile_hint != 0 && (a->tile_hint < HINT_WINO2 || a->tile_hint > HINT_WINO4_FUSED64)) || a->splitk_hint > 0 || a->batch > 1) return false;
   if (a->flags & (GAD_GEMM_NO_WINO | GAD_GEMM_NO_PATCH | GAD_GEMM_SCALAR_EPILOGUE | GAD_GEMM_TAP_MAJOR_K)) return false;
   if (a->rowadd && a->rows_per_group != g.Ho * g.Wo) return false;
   if (a->M % (g.Ho * g.Wo) != 0) return false;
@@ -2721,9 +2722,9 @@ static bool use_wino(const gad_gemm_args* a, WinoPlan* wp) {
                       (!a->rowadd || (gad_aligned16(a->rowadd) && a->ld_rowadd % 4 == 0)) &&
                       (!a->residual || (gad_aligned16(a->residual) && a->ldr % 4 == 0));
   if (!vec_ok) return false;
-  const bool force4 = a->tile_hint >= 8 && a->tile_hint <= 11;   // 8: planner's F(4x4) form, 9 / 11: the one-launch form on 32- / 64-tile blocks, 10: the three-launch forms
+  const bool force4 = a->tile_hint >= HINT_WINO4 && a->tile_hint <= HINT_WINO4_FUSED64;
   const bool f2_ok = a->B_wino != nullptr && (long)a->M / 4 < (1L << 30) && !force4;
-  const bool f4_ok = a->B_wino4 != nullptr && (He & 3) == 0 && (We & 3) == 0 && a->tile_hint != 7;
+  const bool f4_ok = a->B_wino4 != nullptr && (g.Ho & 3) == 0 && (g.Wo & 3) == 0 && a->tile_hint != HINT_WINO2;
   // Modelled times (calibrated on tools/ab_winograd.py, profiles/r03_ab_winograd.txt).  Transform launches stream their bytes
   // at ~4.9 TB/s.  F(2x2): a CU runs the 16-position product of one block at ~0.43 TF/s whether it holds one block or two,
   // so the GEMM takes ceil(blocks / 256) block times.  F(4x4): 36 batched products on 128 x 128 tiles, rounds of 512
@@ -2772,10 +2773,10 @@ static bool use_wino(const gad_gemm_args* a, WinoPlan* wp) {
     const double t_gemm = (double)gad_ceil_div(blocks, 512) * (g.C / BK + 1) * (128.0 * 128.0 * BK * 2.0) / 0.254e12;
     const double mb3 = (p4.fused4 ? 24.0 : 36.0) * p4.T * a->N * 4.0;
     const double t3 = t_gemm + (mb3 + y_bytes) / 4.9e12 + 12e-6;
-    const bool full_ok = !(a->flags & GAD_GEMM_GENERAL_LOADERS) && a->tile_hint != 10;
-    if (full_ok && (a->tile_hint == 9 || a->tile_hint == 11 || (t_full < 1.05 * t3 && blocks32 >= 320))) {
+    const bool full_ok = !(a->flags & GAD_GEMM_GENERAL_LOADERS) && a->tile_hint != HINT_WINO4_THREE;
+    if (full_ok && (a->tile_hint == HINT_WINO4_FUSED32 || a->tile_hint == HINT_WINO4_FUSED64 || (t_full < 1.05 * t3 && blocks32 >= 320))) {
       p4.fused4 = 2;
-      p4.bm = a->tile_hint == 11 ? 64 : narrow ? 65 : 32;       // 65 names the 64-tile x 32-channel shape (64: the one-workgroup-per-CU form kept for A/B)
+      p4.bm = a->tile_hint == HINT_WINO4_FUSED64 ? 64 : narrow ? 65 : 32;       // 65 names the 64-tile x 32-channel shape (64: the one-workgroup-per-CU form kept for A/B)
       p4.bn = p4.bm == 65 ? 32 : 64;
       p4.tiles_m = (int)gad_ceil_div(p4.T, p4.bm == 32 ? 32 : 64);
       p4.tiles_n = (int)gad_ceil_div(a->N, p4.bn);
@@ -2784,8 +2785,8 @@ static bool use_wino(const gad_gemm_args* a, WinoPlan* wp) {
     p4.bytes = (int64_t)(vb + mb);
     t4 = (x_bytes + vb) / 4.9e12 + (p4.fused4 == 2 ? t_full : t3) + 6e-6;
   }
-  if (a->tile_hint == 7 || force4) {             // A/B tools force a route
-    if (a->tile_hint == 7 && f2_ok) { *wp = p2; return true; }
+  if (a->tile_hint == HINT_WINO2 || force4) {    // A/B tools force a route
+    if (a->tile_hint == HINT_WINO2 && f2_ok) { *wp = p2; return true; }
     if (force4 && f4_ok) { *wp = p4; return true; }
     return false;
   }
@@ -2813,10 +2814,9 @@ static bool use_wino_wgrad(const gad_gemm_args* a, WinoWgradPlan* wq) {
   const gad_conv_geom& g = a->g;
   if (!(a->flags & GAD_GEMM_WINO_WGRAD) || (a->flags & (GAD_GEMM_NO_WINO | GAD_GEMM_NO_PATCH | GAD_GEMM_INTERNAL_WINO4))) return false;
   if (a->operand_precision != 0 || a->a_mode != GAD_A_MC || a->b_mode != GAD_B_CONV || a->A2 || a->A_k2 || a->batch > 1) return false;
-  const int He = g.upsample ? 2 * g.H : g.H, We = g.upsample ? 2 * g.W : g.W;
-  if (g.KH != 3 || g.KW != 3 || g.stride != 1 || g.pad_t != 1 || g.pad_l != 1 || g.Ho != He || g.Wo != We || (He & 3) || (We & 3)) return false;
+  if (!same_3x3(g) || (g.Ho & 3) || (g.Wo & 3)) return false;
   if (g.C % 4 != 0 || g.ldx % 4 != 0 || a->M % 4 != 0 || a->lda % 4 != 0 || a->N != 9 * g.C || a->ldc % 4 != 0) return false;
-  if ((a->tile_hint != 0 && a->tile_hint != 8) || a->splitk_hint > 0 || a->K % (g.Ho * g.Wo) != 0) return false;
+  if ((a->tile_hint != 0 && a->tile_hint != HINT_WINO4) || a->splitk_hint > 0 || a->K % (g.Ho * g.Wo) != 0) return false;
   if (a->alpha != 1.f || a->bias || a->rowadd || a->residual) return false;
   if (!(gad_aligned16(a->A) && gad_aligned16(a->B) && gad_aligned16(a->C))) return false;
   wq->T = (long)a->K / 16;
@@ -2824,7 +2824,7 @@ static bool use_wino_wgrad(const gad_gemm_args* a, WinoWgradPlan* wq) {
   wq->v_bytes = (int64_t)36 * wq->T * g.C * 4;
   wq->du_bytes = (int64_t)36 * a->M * g.C * 4;
   wq->bytes = wq->wy_bytes + wq->v_bytes + wq->du_bytes;
-  if (a->tile_hint == 8) return true;
+  if (a->tile_hint == HINT_WINO4) return true;
   const double dy_bytes = 4.0 * a->K * a->M, x_bytes = 4.0 * (double)(a->K / (g.Ho * g.Wo)) * g.H * g.W * g.C;
   const double t_w = (dy_bytes + x_bytes + (double)wq->wy_bytes + (double)wq->v_bytes) / 4.9e12 + 36.0 * wq->T * a->M * (double)g.C * 2.0 / 100e12 +
                      3.0 * (double)wq->du_bytes / 3.0e12 + 30e-6;
@@ -2832,80 +2832,167 @@ static bool use_wino_wgrad(const gad_gemm_args* a, WinoWgradPlan* wq) {
   return t_w < 0.9 * t_direct;
 }
 
-// the 36 batched products dU[pos] = Wy[pos]^T V[pos] of the Winograd weight gradient as a launch of the generic engine
-static void wino_wgrad_sub(const gad_gemm_args* a, const WinoWgradPlan& wq, float* Wy, float* V, float* dU, gad_gemm_args* sub) {
-  *sub = *a;
-  sub->A = Wy; sub->B = V; sub->C = dU;
-  sub->a_mode = GAD_A_MC; sub->b_mode = GAD_B_MC;
-  sub->M = a->M; sub->N = a->g.C; sub->K = (int32_t)wq.T;
-  sub->lda = a->M; sub->ldb = a->g.C; sub->ldc = a->g.C;
-  sub->batch = 36; sub->batch_inner = 1;
-  sub->strideA0 = wq.T * (int64_t)a->M; sub->strideA1 = 0;
-  sub->strideB0 = wq.T * (int64_t)a->g.C; sub->strideB1 = 0;
-  sub->strideC0 = (int64_t)a->M * a->g.C; sub->strideC1 = 0;
-  sub->tile_hint = 0; sub->splitk_hint = 0;
-  sub->flags = GAD_GEMM_INTERNAL_WINO4;
-  sub->B_wino = nullptr; sub->B_wino4 = nullptr; sub->wino_ws = nullptr; sub->wino_ws_bytes = 0;
-  sub->A2 = nullptr;
+// ---- sub-launch arguments: the size queries and the launches build them here, once ----
+
+// the 36 batched products of a Winograd form, C[pos] = A[pos] B[pos] (pos-major panels, no epilogue), as one launch of the
+// generic engine on its own plan (tile shapes measured within 4 % of each other here)
+static gad_gemm_args products36(const gad_gemm_args* a, const float* A, const float* B, float* C, int am, int bm, int M, int N, int K) {
+  gad_gemm_args sub = *a;
+  sub.A = A; sub.B = B; sub.C = C;
+  sub.a_mode = am; sub.b_mode = bm;
+  sub.M = M; sub.N = N; sub.K = K;
+  sub.lda = am == GAD_A_MC ? M : K; sub.ldb = bm == GAD_B_MC ? N : K; sub.ldc = N;
+  sub.batch = 36; sub.batch_inner = 1;
+  sub.strideA0 = (int64_t)M * K; sub.strideB0 = (int64_t)N * K; sub.strideC0 = (int64_t)M * N;
+  sub.strideA1 = sub.strideB1 = sub.strideC1 = 0;
+  sub.tile_hint = 0; sub.splitk_hint = 0;
+  sub.flags = GAD_GEMM_INTERNAL_WINO4;
+  sub.B_wino = nullptr; sub.B_wino4 = nullptr; sub.wino_ws = nullptr; sub.wino_ws_bytes = 0;
+  sub.A2 = nullptr;
+  return sub;
+}
+// weight gradient: dU[pos] = Wy[pos]^T V[pos]
+static gad_gemm_args wino_wgrad_products_args(const gad_gemm_args* a, const WinoWgradPlan& wq, float* Wy, float* V, float* dU) {
+  return products36(a, Wy, V, dU, GAD_A_MC, GAD_B_MC, a->M, a->g.C, (int)wq.T);
+}
+// three-launch F(4x4) forward: M[pos] = V[pos] U[pos]^T, then the output transform applies the epilogue
+static gad_gemm_args wino4_products_args(const gad_gemm_args* a, const WinoPlan& wp, float* V, float* Mb) {
+  gad_gemm_args sub = products36(a, V, a->B_wino4, Mb, GAD_A_KC, GAD_B_KC, (int)wp.T, a->N, a->g.C);
+  sub.alpha = 1.f; sub.bias = nullptr; sub.rowadd = nullptr; sub.residual = nullptr;
+  return sub;
 }
 
-extern "C" int gad_gemm_uses_bf16(const gad_gemm_args* a) {
-  if (!a) return 0;
-  GAD_CANON(a);
-  return use_bf16(a) ? 1 : 0;
+// ---- the route: which kernels run a launch, and on what plan ----
+// route_of is the one place that orders the routes; the size queries and gad_gemm all read the Route it returns.
+enum class RouteKind { ENGINE, PATCH_F32, PATCH_BF16, FEWOUT, WGRAD_PATCH, WINO, WINO_WGRAD, SPLIT_N, SPLIT_M };
+struct Route {
+  RouteKind kind;
+  gad_gemm_args a;           // the canonical arguments (as_dense_1x1)
+  int vec;                   // pick_vec: 4 = the float4 loaders
+  bool bf16;                 // use_bf16: the caller allows bf16 operands and the operands suit the bf16 instances
+  Plan plan;                 // ENGINE
+  PatchPlan pp;              // PATCH_F32; SPLIT_N: the single padded launch the split beats
+  WinoPlan wp;               // WINO
+  WinoWgradPlan wq;          // WINO_WGRAD
+  int wbm, wsplits;          // WGRAD_PATCH, SPLIT_M: output-channel tile and pixel splits
+  int split;                 // SPLIT_N: output columns of the first launch; SPLIT_M: its output rows
+};
+
+static Route route_of(const gad_gemm_args* args) {
+  Route r{};
+  r.a = canonical(args);
+  const gad_gemm_args* a = &r.a;
+  r.vec = pick_vec(a);
+  r.bf16 = use_bf16(a);
+  if (use_wino_wgrad(a, &r.wq)) r.kind = RouteKind::WINO_WGRAD;
+  else if (use_wino(a, &r.wp)) r.kind = RouteKind::WINO;
+  else if (patch_split_n(a, &r.split)) {
+    r.kind = RouteKind::SPLIT_N;
+    use_patch_conv_f32(a, &r.pp);
+  } else if (wgrad_split_m(a, &r.split)) {
+    r.kind = RouteKind::SPLIT_M;
+    r.wsplits = wgrad_patch_splits(a, &r.wbm);
+  } else if (use_fewout_conv(a)) r.kind = RouteKind::FEWOUT;
+  else if ((r.wsplits = wgrad_patch_splits(a, &r.wbm))) r.kind = RouteKind::WGRAD_PATCH;
+  else if (use_patch_conv(a)) r.kind = RouteKind::PATCH_BF16;
+  else if (use_patch_conv_f32(a, &r.pp)) r.kind = RouteKind::PATCH_F32;
+  else {
+    r.kind = RouteKind::ENGINE;
+    r.plan = make_plan(a);
+  }
+  return r;
 }
 
-extern "C" int gad_gemm_kernel_id(const gad_gemm_args* a) {
-  if (!a) return -1;
-  GAD_CANON(a);
-  if (WinoPlan wp; use_wino(a, &wp)) return wp.f == 2 ? 5 : 6;
-  if (WinoWgradPlan wq; use_wino_wgrad(a, &wq)) return 7;
-  if (use_fewout_conv(a)) return 4;
-  if (wgrad_patch_splits(a)) return 2;
-  if (use_patch_conv(a)) return 3;
-  if (use_bf16(a)) return 1;
-  PatchPlan pp;
-  return use_patch_conv_f32(a, &pp) ? 2 : 0;
+// what gad_gemm_kernel_id and gad_gemm_plan report for a route: kernel family, tile, split
+struct Report { int kid, tile, splitk; };
+static Report report(const Route& r) {
+  switch (r.kind) {
+    case RouteKind::ENGINE: return {r.bf16 ? 1 : 0, r.plan.bm, r.plan.splitk};
+    case RouteKind::PATCH_F32: return {2, r.pp.bn, r.pp.splitk};                       // 128 pixels x bn channels
+    case RouteKind::SPLIT_N: return {2, 224, r.pp.splitk};                             // 224: two launches, 128-wide tiles then 96-wide ones
+    case RouteKind::SPLIT_M: return {2, 224, r.wsplits};                               //      (weight gradient: 128-channel tiles, then the rest)
+    case RouteKind::WGRAD_PATCH: return {2, r.wbm, r.wsplits};                         // output channels x pixel splits
+    case RouteKind::PATCH_BF16: return {3, 128, 1};                                    // 128 x 128, never split
+    case RouteKind::FEWOUT: return {4, 256, 1};                                        // 256 pixels x all (<= 4) output channels
+    case RouteKind::WINO: return {r.wp.f == 2 ? 5 : 6, r.wp.f == 2 ? r.wp.bn : (r.wp.fused4 == 2 ? r.wp.bm : 128), 1};   // F(4x4): the block's tiles
+    case RouteKind::WINO_WGRAD: return {7, 128, 1};                                    // 36 batched products on the engine's own plan
+  }
+  return {-1, 0, 0};
 }
+
+// the two launches of SPLIT_N (disjoint output columns) and SPLIT_M (disjoint output rows of a weight gradient)
+static void split_halves(const Route& r, gad_gemm_args* lo, gad_gemm_args* hi) {
+  const gad_gemm_args* a = &r.a;
+  const int s = r.split;
+  *lo = *a;
+  *hi = *a;
+  if (r.kind == RouteKind::SPLIT_M) {
+    if (a->tile_hint >= HINT_SPLIT_M) lo->tile_hint = hi->tile_hint = 0;
+    lo->M = s;
+    hi->M = a->M - s;
+    hi->A = a->A + s;                        // A_MC: dy [pixels][Cout], the output channel is the contiguous index
+    hi->C = a->C + (long)s * a->ldc;
+    return;
+  }
+  lo->B_wino = lo->B_wino4 = hi->B_wino = hi->B_wino4 = nullptr;    // the halves are direct launches: the transformed weights' position stride is the FULL Cout
+  lo->wino_ws = hi->wino_ws = nullptr;
+  lo->wino_ws_bytes = hi->wino_ws_bytes = 0;
+  lo->N = s;
+  hi->N = a->N - s;
+  hi->B = a->B + (long)s * a->ldb;
+  hi->C = a->C + s;
+  if (a->bias) hi->bias = a->bias + s;
+  if (a->rowadd) hi->rowadd = a->rowadd + s;
+  if (a->residual) hi->residual = a->residual + s;
+}
+
+static int64_t workspace_bytes(const Route& r) {
+  const gad_gemm_args* a = &r.a;
+  switch (r.kind) {
+    case RouteKind::ENGINE: case RouteKind::PATCH_F32: case RouteKind::WGRAD_PATCH: case RouteKind::PATCH_BF16: case RouteKind::FEWOUT: {
+      const int splitk = report(r).splitk;              // one M x N slab of partial sums per split (and batch: the engine's)
+      return splitk > 1 ? (int64_t)(a->batch > 0 ? a->batch : 1) * splitk * a->M * a->N * (int64_t)sizeof(float) : 0;
+    }
+    case RouteKind::WINO: {
+      if (r.wp.f == 2 || r.wp.fused4) return 0;         // (the product kernels of both fused forms never split K)
+      const gad_gemm_args sub = wino4_products_args(a, r.wp, nullptr, nullptr);     // the 36 batched products may split K
+      return gad_gemm_workspace_bytes(&sub);
+    }
+    case RouteKind::WINO_WGRAD: {
+      const gad_gemm_args sub = wino_wgrad_products_args(a, r.wq, nullptr, nullptr, nullptr);
+      return gad_gemm_workspace_bytes(&sub);
+    }
+    case RouteKind::SPLIT_N: case RouteKind::SPLIT_M: {   // one launch after the other on the same workspace
+      gad_gemm_args lo, hi;
+      split_halves(r, &lo, &hi);
+      const int64_t wl = gad_gemm_workspace_bytes(&lo), wh = gad_gemm_workspace_bytes(&hi);
+      return wl > wh ? wl : wh;
+    }
+  }
+  return 0;
+}
+
+extern "C" int gad_gemm_uses_bf16(const gad_gemm_args* a) { return a && route_of(a).bf16 ? 1 : 0; }
+
+extern "C" int gad_gemm_kernel_id(const gad_gemm_args* a) { return a ? report(route_of(a)).kid : -1; }
 
 extern "C" int gad_gemm_plan(const gad_gemm_args* a, int32_t* tile, int32_t* splitk, int32_t* vec) {
   GAD_CHECK(a && tile && splitk && vec, "gad_gemm_plan: null pointer");
-  GAD_CANON(a);
-  *vec = pick_vec(a);
-  PatchPlan pp;
-  if (WinoWgradPlan wq; use_wino_wgrad(a, &wq)) {   // Winograd weight gradient: 36 batched products on the engine's own plan
-    *tile = 128;
-    *splitk = 1;
-  } else if (WinoPlan wp; use_wino(a, &wp)) {    // Winograd: bm tiles of 2x2 pixels x bn channels (reported: bn); F(4x4): 128
-    *tile = wp.f == 2 ? wp.bn : (wp.fused4 == 2 ? wp.bm : 128);
-    *splitk = 1;
-  } else if (use_fewout_conv(a)) {               // vector-ALU kernel: 256 pixels x all (<= 4) output channels
-    *tile = 256;
-    *splitk = 1;
-  } else if (int bm = 0; int sp = wgrad_patch_splits(a, &bm)) {   // patch weight gradient: 128 / 96 output channels x pixel splits
-    int m1 = 0;
-    *tile = wgrad_split_m(a, &m1) ? 224 : bm;                 // 224: two launches, 128-channel tiles then 96-channel tiles
-    *splitk = sp;
-  } else if (!use_bf16(a) && use_patch_conv_f32(a, &pp)) {   // patch forward / dgrad: 128 pixels x bn channels
-    int n1 = 0;
-    *tile = patch_split_n(a, &n1) ? 224 : pp.bn;              // 224: two launches, 128-wide tiles then 96-wide tiles
-    *splitk = pp.splitk;
-  } else {
-    Plan pl = make_plan(a);
-    *tile = pl.bm;
-    *splitk = pl.splitk;
-  }
+  const Route r = route_of(a);
+  const Report rep = report(r);
+  *tile = rep.tile;
+  *splitk = rep.splitk;
+  *vec = r.vec;
   return 0;
 }
 
 extern "C" int64_t gad_gemm_wino_bytes(const gad_gemm_args* a) {
   if (!a) return 0;
-  GAD_CANON(a);
-  WinoPlan wp;
-  if (use_wino(a, &wp)) return wp.bytes;
-  WinoWgradPlan wq;
-  return use_wino_wgrad(a, &wq) ? wq.bytes : 0;
+  const Route r = route_of(a);
+  return r.kind == RouteKind::WINO ? r.wp.bytes : r.kind == RouteKind::WINO_WGRAD ? r.wq.bytes : 0;
 }
+
+extern "C" int64_t gad_gemm_workspace_bytes(const gad_gemm_args* a) { return a ? workspace_bytes(route_of(a)) : 0; }
 
 extern "C" int gad_wino_weights(const float* src, float* dst, const int64_t* table, int64_t n_tiles, void* stream) {
   GAD_CHECK(src && dst && table && n_tiles > 0 && n_tiles < (1L << 31), "gad_wino_weights: bad arguments");
@@ -2922,93 +3009,21 @@ extern "C" int gad_wino4_weights(const float* src, float* dst, const int64_t* ta
   return 0;
 }
 
-extern "C" int64_t gad_gemm_workspace_bytes(const gad_gemm_args* a) {
-  GAD_CANON(a);
-  if (WinoWgradPlan wq; use_wino_wgrad(a, &wq)) {
-    gad_gemm_args sub;
-    wino_wgrad_sub(a, wq, nullptr, nullptr, nullptr, &sub);
-    return gad_gemm_workspace_bytes(&sub);
-  }
-  if (WinoPlan wp; use_wino(a, &wp)) {
-    if (wp.f == 2 || wp.fused4) return 0;         // (the product kernels of both fused forms never split K)
-    gad_gemm_args sub = *a;                      // the 36 batched products may split K on small launches
-    sub.B_wino = nullptr; sub.B_wino4 = nullptr;
-    sub.a_mode = GAD_A_KC; sub.b_mode = GAD_B_KC;
-    sub.M = (int32_t)wp.T; sub.K = a->g.C; sub.lda = a->g.C; sub.ldb = a->g.C; sub.ldc = a->N;
-    sub.batch = 36; sub.batch_inner = 1; sub.tile_hint = 0;
-    sub.bias = nullptr; sub.rowadd = nullptr; sub.residual = nullptr; sub.alpha = 1.f;
-    return gad_gemm_workspace_bytes(&sub);
-  }
-  if (use_fewout_conv(a)) return 0;
-  if (int m1 = 0; wgrad_split_m(a, &m1)) {
-    gad_gemm_args lo, hi;
-    wgrad_split_args(a, m1, &lo, &hi);
-    const int64_t wl = gad_gemm_workspace_bytes(&lo), wh = gad_gemm_workspace_bytes(&hi);
-    return wl > wh ? wl : wh;
-  }
-  if (int sp = wgrad_patch_splits(a)) return sp > 1 ? (int64_t)sp * a->M * a->N * (int64_t)sizeof(float) : 0;
-  {
-    PatchPlan pp;
-    if (use_patch_conv_f32(a, &pp)) return pp.splitk > 1 ? (int64_t)pp.splitk * a->M * a->N * (int64_t)sizeof(float) : 0;
-  }
-  Plan pl = make_plan(a);
-  if (pl.splitk == 1) return 0;
-  long batch = a->batch > 0 ? a->batch : 1;
-  return (int64_t)batch * pl.splitk * a->M * a->N * (int64_t)sizeof(float);
-}
+// ---- gad_gemm: check the arguments, resolve the route, dispatch on its kind ----
 
-extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
-  GAD_CHECK(a && a->A && a->B && a->C, "gad_gemm: null pointer");
-  GAD_CANON(a);
+// shape / alignment contracts of the float4 paths (checked on the host so that a mismatch is an error, never an
+// out-of-bounds access on the device)
+static int check_args(const gad_gemm_args* a) {
   GAD_CHECK(a->M > 0 && a->N > 0 && a->K > 0, "gad_gemm: bad shape M=%d N=%d K=%d", a->M, a->N, a->K);
-  WinoPlan wino_first;
-  if (int n1 = 0; !use_wino(a, &wino_first) && patch_split_n(a, &n1)) {          // 224 / 448 output channels: 128-wide tiles, then 96-wide tiles
-    gad_gemm_args lo = *a, hi = *a;
-    lo.B_wino = lo.B_wino4 = hi.B_wino = hi.B_wino4 = nullptr;    // the halves are direct launches: the transformed weights' position stride is the FULL Cout
-    lo.wino_ws = hi.wino_ws = nullptr;
-    lo.wino_ws_bytes = hi.wino_ws_bytes = 0;
-    lo.N = n1;
-    hi.N = a->N - n1;
-    hi.B = a->B + (long)n1 * a->ldb;
-    hi.C = a->C + n1;
-    if (a->bias) hi.bias = a->bias + n1;
-    if (a->rowadd) hi.rowadd = a->rowadd + n1;
-    if (a->residual) hi.residual = a->residual + n1;
-    const int rc = gad_gemm(&lo, stream);
-    return rc ? rc : gad_gemm(&hi, stream);
-  }
-  WinoWgradPlan wgrad_first;
-  if (int m1 = 0; !use_wino_wgrad(a, &wgrad_first) && wgrad_split_m(a, &m1)) {
-    gad_gemm_args lo, hi;
-    wgrad_split_args(a, m1, &lo, &hi);
-    const int rc = gad_gemm(&lo, stream);
-    return rc ? rc : gad_gemm(&hi, stream);
-  }
   const int am = a->a_mode, bmode = a->b_mode;
-  const bool convA = am == GAD_A_CONV || am == GAD_A_CONVT;
-  const bool geomB = bmode == GAD_B_CONV || bmode == GAD_B_WDGRAD;
-  int vec = pick_vec(a);
-  // --- shape / alignment contracts of the float4 paths (checked on the host so that a
-  //     mismatch is an error, never an out-of-bounds access on the device) ---
   GAD_CHECK(gad_aligned16(a->A) && gad_aligned16(a->B), "gad_gemm: A/B must be 16-byte aligned");
   const int k_first = a->A_k2 ? a->k_split : a->K;      // K-concatenated form: the first tensor covers k < k_split only
-  if (am == GAD_A_KC) {
-    GAD_CHECK(a->lda >= k_first, "gad_gemm: A_KC needs lda >= K (K=%d lda=%d)", k_first, a->lda);
-    if (a->K % 4 != 0 || a->lda % 4 != 0) vec = 1;
-  }
-  if (am == GAD_A_MC) {
-    GAD_CHECK(a->lda >= a->M, "gad_gemm: A_MC needs lda >= M (M=%d lda=%d)", a->M, a->lda);
-    if (a->M % 4 != 0 || a->lda % 4 != 0) vec = 1;
-  }
-  if (bmode == GAD_B_KC) {
-    GAD_CHECK(a->ldb >= k_first, "gad_gemm: B_KC needs ldb >= K (K=%d ldb=%d)", k_first, a->ldb);
-    if (a->K % 4 != 0 || a->ldb % 4 != 0) vec = 1;
-  }
-  if (bmode == GAD_B_MC) {
-    GAD_CHECK(a->ldb >= a->N, "gad_gemm: B_MC needs ldb >= N (N=%d ldb=%d)", a->N, a->ldb);
-    if (a->N % 4 != 0 || a->ldb % 4 != 0) vec = 1;
-  }
-  if (convA || geomB) {
+  if (am == GAD_A_KC) GAD_CHECK(a->lda >= k_first, "gad_gemm: A_KC needs lda >= K (K=%d lda=%d)", k_first, a->lda);
+  if (am == GAD_A_MC) GAD_CHECK(a->lda >= a->M, "gad_gemm: A_MC needs lda >= M (M=%d lda=%d)", a->M, a->lda);
+  if (bmode == GAD_B_KC) GAD_CHECK(a->ldb >= k_first, "gad_gemm: B_KC needs ldb >= K (K=%d ldb=%d)", k_first, a->ldb);
+  if (bmode == GAD_B_MC) GAD_CHECK(a->ldb >= a->N, "gad_gemm: B_MC needs ldb >= N (N=%d ldb=%d)", a->N, a->ldb);
+  const bool convA = am == GAD_A_CONV || am == GAD_A_CONVT;
+  if (convA || bmode == GAD_B_CONV || bmode == GAD_B_WDGRAD) {
     const gad_conv_geom& g = a->g;
     GAD_CHECK(g.H > 0 && g.W > 0 && g.C > 0 && g.Ho > 0 && g.Wo > 0 && g.KH > 0 && g.KW > 0 && g.stride > 0 &&
               g.ldx >= (a->A2 ? a->a_split : g.C), "gad_gemm: bad conv geometry");
@@ -3017,7 +3032,6 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
       GAD_CHECK(a->K == g.KH * g.KW * g.C, "gad_gemm: conv K=%d != KH*KW*C=%d", a->K, g.KH * g.KW * g.C);
       GAD_CHECK(a->M % (g.Ho * g.Wo) == 0, "gad_gemm: conv M=%d not a multiple of Ho*Wo", a->M);
       GAD_CHECK((long)(a->M / (g.Ho * g.Wo)) * g.H * g.W < (1L << 31), "gad_gemm: too many pixels");
-      if (g.C % 4 != 0 || g.ldx % 4 != 0) vec = 1;
     }
     if (bmode == GAD_B_WDGRAD) {
       GAD_CHECK(am == GAD_A_CONVT, "gad_gemm: B_WDGRAD pairs with A_CONVT");
@@ -3027,9 +3041,9 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
       GAD_CHECK(a->N == g.KH * g.KW * g.C, "gad_gemm: wgrad N=%d != KH*KW*C=%d", a->N, g.KH * g.KW * g.C);
       GAD_CHECK(a->K % (g.Ho * g.Wo) == 0, "gad_gemm: wgrad K=%d not a multiple of Ho*Wo", a->K);
       GAD_CHECK((long)(a->K / (g.Ho * g.Wo)) * g.H * g.W < (1L << 31), "gad_gemm: too many pixels");
-      if (g.C % 4 != 0 || g.ldx % 4 != 0) vec = 1;
     }
   }
+  const int vec = pick_vec(a);
   if (a->A2) {
     GAD_CHECK(am == GAD_A_CONV && bmode == GAD_B_KC, "gad_gemm: A2 (two-source gather) is an A_CONV x B_KC feature");
     GAD_CHECK(a->a_split > 0 && a->a_split < a->g.C && a->a_split % 32 == 0 && a->g.C % 32 == 0,
@@ -3037,8 +3051,7 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
     GAD_CHECK(a->ldx2 >= a->g.C - a->a_split && a->ldx2 % 4 == 0 && gad_aligned16(a->A2) && vec == 4,
               "gad_gemm: two-source gather: bad ldx2 / alignment");
   }
-  const bool ksplit2 = a->A_k2 != nullptr;
-  if (ksplit2) {
+  if (a->A_k2) {
     GAD_CHECK(am == GAD_A_KC && (bmode == GAD_B_KC || bmode == GAD_B_MC) && a->B_k2 && !a->A2 && a->batch <= 1,
               "gad_gemm: the K-concatenated form (A_k2 / B_k2) is an A_KC x B_KC|B_MC feature");
     GAD_CHECK(a->k_split > 0 && a->k_split < a->K && a->k_split % 32 == 0, "gad_gemm: k_split must be a multiple of 32 inside (0, K) (k_split=%d K=%d)", a->k_split, a->K);
@@ -3052,9 +3065,23 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
   if (a->rowadd) GAD_CHECK(a->rows_per_group > 0 && a->ld_rowadd >= a->N, "gad_gemm: bad rowadd");
   if (a->residual) GAD_CHECK(a->ldr >= a->N, "gad_gemm: bad residual stride");
   GAD_CHECK(a->ldc >= a->N, "gad_gemm: ldc < N");
+  GAD_CHECK(a->operand_precision == 0 || a->operand_precision == 1, "gad_gemm: operand_precision must be 0 (f32) or 1 (bf16 allowed)");
+  return 0;
+}
 
-  long batch = a->batch > 0 ? a->batch : 1;
+// GAD_GEMM_WINO_ONLY_INPUT / _SKIP_INPUT run one stage of a Winograd launch: on any other route they would silently run a
+// direct kernel that reads A (which a caller holding only the transformed image does not have), so they are refused there
+static int check_stage_flags(const Route& r) {
+  const bool only_input = (r.a.flags & GAD_GEMM_WINO_ONLY_INPUT) != 0, skip_input = (r.a.flags & GAD_GEMM_WINO_SKIP_INPUT) != 0;
+  GAD_CHECK(!(only_input && skip_input), "gad_gemm: GAD_GEMM_WINO_ONLY_INPUT and GAD_GEMM_WINO_SKIP_INPUT exclude each other");
+  GAD_CHECK(!only_input || r.kind == RouteKind::WINO,
+            "gad_gemm: GAD_GEMM_WINO_ONLY_INPUT on a launch that takes no Winograd forward route (kernel id %d)", report(r).kid);
+  GAD_CHECK(!skip_input || r.kind == RouteKind::WINO || r.kind == RouteKind::WINO_WGRAD,
+            "gad_gemm: GAD_GEMM_WINO_SKIP_INPUT on a launch that takes no Winograd route (kernel id %d)", report(r).kid);
+  return 0;
+}
 
+static DevArgs dev_args(const gad_gemm_args* a) {
   DevArgs d;
   d.A = a->A; d.B = a->B; d.C = a->C;
   d.A2 = a->A2; d.a_split = a->a_split; d.ldx2 = a->ldx2;
@@ -3073,6 +3100,7 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
   d.fdRpg = make_fastdiv(a->rows_per_group > 0 ? a->rows_per_group : 1);
   d.taps = a->g.KH * a->g.KW;
   d.fdTaps = make_fastdiv(d.taps > 0 ? d.taps : 1);
+  const bool convA = a->a_mode == GAD_A_CONV || a->a_mode == GAD_A_CONVT;
   d.kperm = (convA && d.taps > 1 && a->g.C % BK == 0 && !(a->flags & GAD_GEMM_TAP_MAJOR_K)) ? 1 : 0;
   d.alpha = a->alpha;
   d.bias = a->bias; d.rowadd = a->rowadd; d.rows_per_group = a->rows_per_group > 0 ? a->rows_per_group : 1;
@@ -3084,237 +3112,239 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
                a->strideC0 % 4 == 0 && a->strideC1 % 4 == 0 && (!a->bias || gad_aligned16(a->bias)) &&
                (!a->rowadd || (gad_aligned16(a->rowadd) && a->ld_rowadd % 4 == 0)) &&
                (!a->residual || (gad_aligned16(a->residual) && a->ldr % 4 == 0)) && (!a->ws || gad_aligned16(a->ws))) ? 1 : 0;
+  return d;
+}
 
+static int launch_wino_wgrad(const Route& r, void* stream) {
+  const gad_gemm_args* a = &r.a;
+  const WinoWgradPlan& wq = r.wq;
+  const gad_conv_geom& g = a->g;
   hipStream_t st = (hipStream_t)stream;
-  GAD_CHECK(a->operand_precision == 0 || a->operand_precision == 1, "gad_gemm: operand_precision must be 0 (f32) or 1 (bf16 allowed)");
-  const bool bf16 = use_bf16(a) && vec == 4;
-  if (WinoWgradPlan wq; use_wino_wgrad(a, &wq)) {
-    GAD_CHECK(a->wino_ws && a->wino_ws_bytes >= wq.bytes && gad_aligned16(a->wino_ws),
-              "gad_gemm: Winograd weight-gradient workspace too small or misaligned (%lld < %lld)", (long long)a->wino_ws_bytes, (long long)wq.bytes);
-    const gad_conv_geom& g = a->g;
-    float* Wy = (float*)a->wino_ws;
-    float* V = Wy + wq.wy_bytes / 4;
-    float* dU = V + wq.v_bytes / 4;
-    // the forward launch of the same convolution already made B^T x B (its V, same geometry => same [36][T][Cin] image): a caller
-    // that kept it passes it as B_wino4 with GAD_GEMM_WINO_SKIP_INPUT and the input transform is not run again
-    const bool have_v = (a->flags & GAD_GEMM_WINO_SKIP_INPUT) && a->B_wino4 != nullptr;
-    if (have_v) {
-      GAD_CHECK(gad_aligned16(a->B_wino4), "gad_gemm: the kept Winograd input image (B_wino4 of a weight-gradient launch) must be 16-byte aligned");
-      V = const_cast<float*>(a->B_wino4);
-    }
-    WinoIn wy;                                     // dy [B][Ho][Wo][Cout] -> Wy
-    wy.x = a->A; wy.V = Wy;
-    wy.H = g.Ho; wy.W = g.Wo; wy.C = a->M; wy.ldx = a->lda; wy.up = 0;
-    wy.TH = g.Ho / 4; wy.TW = g.Wo / 4; wy.T = wq.T;
-    WinoIn wi;                                     // x -> V, as in the forward pass
-    wi.x = a->B; wi.V = V;
-    wi.H = g.H; wi.W = g.W; wi.C = g.C; wi.ldx = g.ldx; wi.up = g.upsample ? 1 : 0;
-    wi.TH = wy.TH; wi.TW = wy.TW; wi.T = wq.T;
-    const long iy = wq.T * (a->M / 4), ix = wq.T * (g.C / 4);
-    GAD_CHECK(gad_ceil_div(iy, 256) < (1L << 31) && gad_ceil_div(ix, 256) < (1L << 31), "gad_gemm: Winograd transform grid too large");
-    hipLaunchKernelGGL(wino4_dy_kernel, dim3((unsigned)gad_ceil_div(iy, 256)), dim3(256), 0, st, wy);
-    if (!have_v) hipLaunchKernelGGL(wino4_input_kernel, dim3((unsigned)gad_ceil_div(ix, 256)), dim3(256), 0, st, wi);
-    GAD_LAUNCH_CHECK("gad_gemm(winograd wgrad transforms)");
-    gad_gemm_args sub;
-    wino_wgrad_sub(a, wq, Wy, V, dU, &sub);
-    if (const int rc = gad_gemm(&sub, stream)) return rc;
-    const long items = (long)a->M * (g.C / 4);
-    hipLaunchKernelGGL(wino4_dw_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, dU, a->C, a->M, g.C, a->ldc);
-    GAD_LAUNCH_CHECK("gad_gemm(winograd wgrad output transform)");
-    return 0;
+  GAD_CHECK(a->wino_ws && a->wino_ws_bytes >= wq.bytes && gad_aligned16(a->wino_ws),
+            "gad_gemm: Winograd weight-gradient workspace too small or misaligned (%lld < %lld)", (long long)a->wino_ws_bytes, (long long)wq.bytes);
+  float* Wy = (float*)a->wino_ws;
+  float* V = Wy + wq.wy_bytes / 4;
+  float* dU = V + wq.v_bytes / 4;
+  // the forward launch of the same convolution already made B^T x B (its V, same geometry => same [36][T][Cin] image): a caller
+  // that kept it passes it as B_wino4 with GAD_GEMM_WINO_SKIP_INPUT and the input transform is not run again
+  const bool have_v = (a->flags & GAD_GEMM_WINO_SKIP_INPUT) && a->B_wino4 != nullptr;
+  if (have_v) {
+    GAD_CHECK(gad_aligned16(a->B_wino4), "gad_gemm: the kept Winograd input image (B_wino4 of a weight-gradient launch) must be 16-byte aligned");
+    V = const_cast<float*>(a->B_wino4);
   }
-  if (WinoPlan wp; use_wino(a, &wp)) {
-    GAD_CHECK(a->wino_ws && a->wino_ws_bytes >= wp.bytes && gad_aligned16(a->wino_ws) && gad_aligned16(wp.f == 2 ? a->B_wino : a->B_wino4),
-              "gad_gemm: Winograd workspace too small or misaligned (%lld < %lld)", (long long)a->wino_ws_bytes, (long long)wp.bytes);
-    const gad_conv_geom& g = a->g;
-    WinoIn wi;
-    wi.x = a->A; wi.V = (float*)a->wino_ws;
-    wi.H = g.H; wi.W = g.W; wi.C = g.C; wi.ldx = g.ldx; wi.up = g.upsample ? 1 : 0;
-    wi.TH = g.Ho / wp.f; wi.TW = g.Wo / wp.f; wi.T = wp.T;
-    const long items = wp.T * (g.C / 4);
-    GAD_CHECK(gad_ceil_div(items, 256) < (1L << 31), "gad_gemm: Winograd input transform grid too large");
-    const bool only_input = (a->flags & GAD_GEMM_WINO_ONLY_INPUT) != 0, skip_input = (a->flags & GAD_GEMM_WINO_SKIP_INPUT) != 0;
-    GAD_CHECK(!(only_input && skip_input), "gad_gemm: GAD_GEMM_WINO_ONLY_INPUT and GAD_GEMM_WINO_SKIP_INPUT exclude each other");
-    if (wp.f == 4) {
-      if (!skip_input) {
-        hipLaunchKernelGGL(wino4_input_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, wi);
-        GAD_LAUNCH_CHECK("gad_gemm(winograd F4 input transform)");
-      }
-      if (only_input) return 0;
-      if (wp.fused4 == 2) {                        // products + the whole output transform in one launch
-        DevArgs w = d;
-        w.A = wi.V; w.B = a->B_wino4;
-        w.M = (int)wp.T; w.N = a->N; w.K = g.C;
-        w.lda = g.C; w.ldb = g.C;
-        w.sA0 = wp.T * (long)g.C; w.sB0 = (long)a->N * g.C;
-        w.fdHoWo = make_fastdiv((unsigned)(wi.TH * wi.TW));
-        w.fdWo = make_fastdiv((unsigned)wi.TW);
-        w.tiles_m = wp.tiles_m; w.tiles_n = wp.tiles_n;
-        GAD_CHECK((long)wp.tiles_m * wp.tiles_n < (1L << 31), "gad_gemm: Winograd grid too large");
-        gadk::launch_wino4_fused(w, wp.bm, st);
-        GAD_LAUNCH_CHECK("gad_gemm(winograd F4 fused products + output transform)");
-        return 0;
-      }
-      float* Mb = wi.V + 36 * wp.T * (long)g.C;
-      WinoOut wo;
-      wo.Mb = Mb; wo.y = a->C; wo.bias = a->bias; wo.rowadd = a->rowadd; wo.residual = a->residual;
-      wo.N = a->N; wo.ldc = a->ldc; wo.ldr = a->ldr; wo.ld_rowadd = a->ld_rowadd;
-      wo.Ho = g.Ho; wo.Wo = g.Wo; wo.TH = wi.TH; wo.TW = wi.TW; wo.T = wp.T; wo.alpha = a->alpha;
-      const long oitems = wp.T * (a->N / 4);
-      if (wp.fused4 == 1) {
-        DevArgs w = d;
-        w.A = wi.V; w.B = a->B_wino4; w.C = Mb;
-        w.M = (int)wp.T; w.N = a->N; w.K = g.C;
-        w.lda = g.C; w.ldb = g.C; w.ldc = a->N;
-        w.sA0 = wp.T * (long)g.C; w.sB0 = (long)a->N * g.C; w.sC0 = wp.T * (long)a->N;
-        w.tiles_m = wp.tiles_m; w.tiles_n = wp.tiles_n;
-        w.splitk = 1; w.bias = nullptr; w.rowadd = nullptr; w.residual = nullptr; w.alpha = 1.f;
-        w.epi_vec = 1;                             // Mh is 16-byte aligned scratch, N % 4 == 0
-        dim3 grid((unsigned)((long)wp.tiles_m * wp.tiles_n * 6)), block(NTHREADS);
-        if (wp.bm == 64) hipLaunchKernelGGL((wino4_gemm_kernel<64, 128>), grid, block, 0, st, w);
-        else hipLaunchKernelGGL((wino4_gemm_kernel<128, 64>), grid, block, 0, st, w);
-        GAD_LAUNCH_CHECK("gad_gemm(winograd F4 products)");
-        hipLaunchKernelGGL(wino4_output_kernel<true>, dim3((unsigned)gad_ceil_div(oitems, 256)), dim3(256), 0, st, wo);
-        GAD_LAUNCH_CHECK("gad_gemm(winograd F4 output transform)");
-        return 0;
-      }
-      gad_gemm_args sub = *a;
-      sub.A = wi.V; sub.B = a->B_wino4; sub.C = Mb;
-      sub.B_wino = nullptr; sub.B_wino4 = nullptr; sub.wino_ws = nullptr; sub.wino_ws_bytes = 0;
-      sub.a_mode = GAD_A_KC; sub.b_mode = GAD_B_KC;
-      sub.M = (int32_t)wp.T; sub.N = a->N; sub.K = g.C;
-      sub.lda = g.C; sub.ldb = g.C; sub.ldc = a->N;
-      sub.batch = 36; sub.batch_inner = 1;
-      sub.strideA0 = wp.T * (int64_t)g.C; sub.strideA1 = 0;
-      sub.strideB0 = (int64_t)a->N * g.C; sub.strideB1 = 0;
-      sub.strideC0 = wp.T * (int64_t)a->N; sub.strideC1 = 0;
-      sub.alpha = 1.f; sub.bias = nullptr; sub.rowadd = nullptr; sub.residual = nullptr;
-      sub.tile_hint = 0; sub.splitk_hint = 0;        // tile shapes measured within 4 % of each other here: the engine's own plan
-      sub.flags = GAD_GEMM_INTERNAL_WINO4;
-      if (const int rc = gad_gemm(&sub, stream)) return rc;
-      hipLaunchKernelGGL(wino4_output_kernel<false>, dim3((unsigned)gad_ceil_div(oitems, 256)), dim3(256), 0, st, wo);
-      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 output transform)");
-      return 0;
-    }
-    if (!skip_input) {
-      hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, wi);
-      GAD_LAUNCH_CHECK("gad_gemm(winograd input transform)");
-    }
-    if (only_input) return 0;
+  WinoIn wy;                                     // dy [B][Ho][Wo][Cout] -> Wy
+  wy.x = a->A; wy.V = Wy;
+  wy.H = g.Ho; wy.W = g.Wo; wy.C = a->M; wy.ldx = a->lda; wy.up = 0;
+  wy.TH = g.Ho / 4; wy.TW = g.Wo / 4; wy.T = wq.T;
+  WinoIn wi;                                     // x -> V, as in the forward pass
+  wi.x = a->B; wi.V = V;
+  wi.H = g.H; wi.W = g.W; wi.C = g.C; wi.ldx = g.ldx; wi.up = g.upsample ? 1 : 0;
+  wi.TH = wy.TH; wi.TW = wy.TW; wi.T = wq.T;
+  const long iy = wq.T * (a->M / 4), ix = wq.T * (g.C / 4);
+  GAD_CHECK(gad_ceil_div(iy, 256) < (1L << 31) && gad_ceil_div(ix, 256) < (1L << 31), "gad_gemm: Winograd transform grid too large");
+  hipLaunchKernelGGL(wino4_dy_kernel, dim3((unsigned)gad_ceil_div(iy, 256)), dim3(256), 0, st, wy);
+  if (!have_v) hipLaunchKernelGGL(wino4_input_kernel, dim3((unsigned)gad_ceil_div(ix, 256)), dim3(256), 0, st, wi);
+  GAD_LAUNCH_CHECK("gad_gemm(winograd wgrad transforms)");
+  const gad_gemm_args sub = wino_wgrad_products_args(a, wq, Wy, V, dU);
+  if (const int rc = gad_gemm(&sub, stream)) return rc;
+  const long items = (long)a->M * (g.C / 4);
+  hipLaunchKernelGGL(wino4_dw_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, dU, a->C, a->M, g.C, a->ldc);
+  GAD_LAUNCH_CHECK("gad_gemm(winograd wgrad output transform)");
+  return 0;
+}
+
+static int launch_wino(const Route& r, const DevArgs& d, void* stream) {
+  const gad_gemm_args* a = &r.a;
+  const WinoPlan& wp = r.wp;
+  const gad_conv_geom& g = a->g;
+  hipStream_t st = (hipStream_t)stream;
+  GAD_CHECK(a->wino_ws && a->wino_ws_bytes >= wp.bytes && gad_aligned16(a->wino_ws) && gad_aligned16(wp.f == 2 ? a->B_wino : a->B_wino4),
+            "gad_gemm: Winograd workspace too small or misaligned (%lld < %lld)", (long long)a->wino_ws_bytes, (long long)wp.bytes);
+  WinoIn wi;
+  wi.x = a->A; wi.V = (float*)a->wino_ws;
+  wi.H = g.H; wi.W = g.W; wi.C = g.C; wi.ldx = g.ldx; wi.up = g.upsample ? 1 : 0;
+  wi.TH = g.Ho / wp.f; wi.TW = g.Wo / wp.f; wi.T = wp.T;
+  const long items = wp.T * (g.C / 4);
+  GAD_CHECK(gad_ceil_div(items, 256) < (1L << 31), "gad_gemm: Winograd input transform grid too large");
+  const bool only_input = (a->flags & GAD_GEMM_WINO_ONLY_INPUT) != 0, skip_input = (a->flags & GAD_GEMM_WINO_SKIP_INPUT) != 0;
+  auto products = [&](const float* U) {          // the product kernels of F(2x2) and of the one-launch F(4x4): V x U + output transform
     DevArgs w = d;
-    w.A = wi.V; w.B = a->B_wino;
+    w.A = wi.V; w.B = U;
     w.M = (int)wp.T; w.N = a->N; w.K = g.C;
     w.lda = g.C; w.ldb = g.C;
     w.sA0 = wp.T * (long)g.C; w.sB0 = (long)a->N * g.C;
     w.fdHoWo = make_fastdiv((unsigned)(wi.TH * wi.TW));
     w.fdWo = make_fastdiv((unsigned)wi.TW);
     w.tiles_m = wp.tiles_m; w.tiles_n = wp.tiles_n;
-    dim3 grid((unsigned)((long)wp.tiles_m * wp.tiles_n)), block(NTHREADS);
-    if (wp.bm == 64) hipLaunchKernelGGL((wino_gemm_kernel<64, 128>), grid, block, 0, st, w);
-    else hipLaunchKernelGGL((wino_gemm_kernel<128, 64>), grid, block, 0, st, w);
-    GAD_LAUNCH_CHECK("gad_gemm(winograd)");
+    return w;
+  };
+  if (wp.f == 4) {
+    if (!skip_input) {
+      hipLaunchKernelGGL(wino4_input_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, wi);
+      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 input transform)");
+    }
+    if (only_input) return 0;
+    if (wp.fused4 == 2) {                        // products + the whole output transform in one launch
+      GAD_CHECK((long)wp.tiles_m * wp.tiles_n < (1L << 31), "gad_gemm: Winograd grid too large");
+      gadk::launch_wino4_fused(products(a->B_wino4), wp.bm, st);
+      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 fused products + output transform)");
+      return 0;
+    }
+    float* Mb = wi.V + 36 * wp.T * (long)g.C;
+    WinoOut wo;
+    wo.Mb = Mb; wo.y = a->C; wo.bias = a->bias; wo.rowadd = a->rowadd; wo.residual = a->residual;
+    wo.N = a->N; wo.ldc = a->ldc; wo.ldr = a->ldr; wo.ld_rowadd = a->ld_rowadd;
+    wo.Ho = g.Ho; wo.Wo = g.Wo; wo.TH = wi.TH; wo.TW = wi.TW; wo.T = wp.T; wo.alpha = a->alpha;
+    const long oitems = wp.T * (a->N / 4);
+    if (wp.fused4 == 1) {
+      DevArgs w = d;
+      w.A = wi.V; w.B = a->B_wino4; w.C = Mb;
+      w.M = (int)wp.T; w.N = a->N; w.K = g.C;
+      w.lda = g.C; w.ldb = g.C; w.ldc = a->N;
+      w.sA0 = wp.T * (long)g.C; w.sB0 = (long)a->N * g.C; w.sC0 = wp.T * (long)a->N;
+      w.tiles_m = wp.tiles_m; w.tiles_n = wp.tiles_n;
+      w.splitk = 1; w.bias = nullptr; w.rowadd = nullptr; w.residual = nullptr; w.alpha = 1.f;
+      w.epi_vec = 1;                             // Mh is 16-byte aligned scratch, N % 4 == 0
+      dim3 grid((unsigned)((long)wp.tiles_m * wp.tiles_n * 6)), block(NTHREADS);
+      if (wp.bm == 64) hipLaunchKernelGGL((wino4_gemm_kernel<64, 128>), grid, block, 0, st, w);
+      else hipLaunchKernelGGL((wino4_gemm_kernel<128, 64>), grid, block, 0, st, w);
+      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 products)");
+      hipLaunchKernelGGL(wino4_output_kernel<true>, dim3((unsigned)gad_ceil_div(oitems, 256)), dim3(256), 0, st, wo);
+      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 output transform)");
+      return 0;
+    }
+    const gad_gemm_args sub = wino4_products_args(a, wp, wi.V, Mb);
+    if (const int rc = gad_gemm(&sub, stream)) return rc;
+    hipLaunchKernelGGL(wino4_output_kernel<false>, dim3((unsigned)gad_ceil_div(oitems, 256)), dim3(256), 0, st, wo);
+    GAD_LAUNCH_CHECK("gad_gemm(winograd F4 output transform)");
     return 0;
   }
-  if (use_fewout_conv(a)) {
-    dim3 grid((unsigned)(a->M / 256)), block(NTHREADS);
+  if (!skip_input) {
+    hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, wi);
+    GAD_LAUNCH_CHECK("gad_gemm(winograd input transform)");
+  }
+  if (only_input) return 0;
+  const DevArgs w = products(a->B_wino);
+  dim3 grid((unsigned)((long)wp.tiles_m * wp.tiles_n)), block(NTHREADS);
+  if (wp.bm == 64) hipLaunchKernelGGL((wino_gemm_kernel<64, 128>), grid, block, 0, st, w);
+  else hipLaunchKernelGGL((wino_gemm_kernel<128, 64>), grid, block, 0, st, w);
+  GAD_LAUNCH_CHECK("gad_gemm(winograd)");
+  return 0;
+}
+
+static int launch_fewout(const Route& r, const DevArgs& d, hipStream_t st) {
+  const gad_gemm_args* a = &r.a;
+  dim3 grid((unsigned)(a->M / 256)), block(NTHREADS);
 #define GAD_FEWOUT(W_)                                                                          \
-    do {                                                                                        \
-      if (a->N <= 3) hipLaunchKernelGGL((conv3x3_fewout_kernel<W_, 3>), grid, block, 0, st, d); \
-      else hipLaunchKernelGGL((conv3x3_fewout_kernel<W_, 4>), grid, block, 0, st, d);           \
-    } while (0)
-    if (a->g.W == 64) GAD_FEWOUT(64);
-    else if (a->g.W == 32) GAD_FEWOUT(32);
-    else GAD_FEWOUT(16);
+  do {                                                                                          \
+    if (a->N <= 3) hipLaunchKernelGGL((conv3x3_fewout_kernel<W_, 3>), grid, block, 0, st, d);   \
+    else hipLaunchKernelGGL((conv3x3_fewout_kernel<W_, 4>), grid, block, 0, st, d);             \
+  } while (0)
+  if (a->g.W == 64) GAD_FEWOUT(64);
+  else if (a->g.W == 32) GAD_FEWOUT(32);
+  else GAD_FEWOUT(16);
 #undef GAD_FEWOUT
-    GAD_LAUNCH_CHECK("gad_gemm(conv3x3 few outputs)");
-    return 0;
+  GAD_LAUNCH_CHECK("gad_gemm(conv3x3 few outputs)");
+  return 0;
+}
+
+static int launch_wgrad_patch(const Route& r, DevArgs& d, hipStream_t st) {
+  const gad_gemm_args* a = &r.a;
+  const int wbm = r.wbm;
+  const long ksteps = a->K / BK;
+  d.tiles_m = (int)gad_ceil_div(a->M, wbm);
+  d.ktiles_per_split = (int)gad_ceil_div(ksteps, r.wsplits);
+  d.splitk = (int)gad_ceil_div(ksteps, d.ktiles_per_split);
+  if (d.splitk > 1) {
+    int64_t need = (int64_t)d.splitk * a->M * a->N * (int64_t)sizeof(float);
+    GAD_CHECK(a->ws && a->ws_bytes >= need, "gad_gemm: wgrad workspace too small (%lld < %lld)", (long long)a->ws_bytes, (long long)need);
   }
-  int wbm = 128;
-  if (int sp = wgrad_patch_splits(a, &wbm)) {
-    const long ksteps = a->K / BK;
-    d.tiles_m = (int)gad_ceil_div(a->M, wbm);
-    d.ktiles_per_split = (int)gad_ceil_div(ksteps, sp);
-    d.splitk = (int)gad_ceil_div(ksteps, d.ktiles_per_split);
-    if (d.splitk > 1) {
-      int64_t need = (int64_t)d.splitk * a->M * a->N * (int64_t)sizeof(float);
-      GAD_CHECK(a->ws && a->ws_bytes >= need, "gad_gemm: wgrad workspace too small (%lld < %lld)", (long long)a->ws_bytes, (long long)need);
-    }
-    dim3 grid((unsigned)(d.splitk * d.tiles_m * (a->g.C / BK))), block(NTHREADS);
+  dim3 grid((unsigned)(d.splitk * d.tiles_m * (a->g.C / BK))), block(NTHREADS);
 #define GAD_WGRAD(W_)                                                                                   \
-    do {                                                                                                \
-      if (wbm == 96) hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 96>), grid, block, 0, st, d);    \
-      else if (wbm == 64) hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 64>), grid, block, 0, st, d);  \
-      else if (wbm == 32) hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 32>), grid, block, 0, st, d);  \
-      else hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 128>), grid, block, 0, st, d);             \
-    } while (0)
-    if (a->g.Wo == 64) GAD_WGRAD(64);
-    else if (a->g.Wo == 32) GAD_WGRAD(32);
-    else if (a->g.Wo == 16) GAD_WGRAD(16);
-    else GAD_WGRAD(8);
+  do {                                                                                                  \
+    if (wbm == 96) hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 96>), grid, block, 0, st, d);      \
+    else if (wbm == 64) hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 64>), grid, block, 0, st, d); \
+    else if (wbm == 32) hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 32>), grid, block, 0, st, d); \
+    else hipLaunchKernelGGL((wgrad3x3_patch_f32_kernel<W_, 128>), grid, block, 0, st, d);               \
+  } while (0)
+  if (a->g.Wo == 64) GAD_WGRAD(64);
+  else if (a->g.Wo == 32) GAD_WGRAD(32);
+  else if (a->g.Wo == 16) GAD_WGRAD(16);
+  else GAD_WGRAD(8);
 #undef GAD_WGRAD
-    GAD_LAUNCH_CHECK("gad_gemm(wgrad3x3 patch)");
-    if (d.splitk > 1) {
-      launch_splitk_reduce(d, 1, st);
-      GAD_LAUNCH_CHECK("gad_gemm(wgrad splitk reduce)");
-    }
-    return 0;
+  GAD_LAUNCH_CHECK("gad_gemm(wgrad3x3 patch)");
+  if (d.splitk > 1) {
+    launch_splitk_reduce(d, 1, st);
+    GAD_LAUNCH_CHECK("gad_gemm(wgrad splitk reduce)");
   }
-  if (bf16 && use_patch_conv(a)) {
-    d.tiles_m = (int)gad_ceil_div(a->M, 128);
-    d.tiles_n = (int)gad_ceil_div(a->N, 128);
-    d.splitk = 1;
-    dim3 grid((unsigned)(d.tiles_m * d.tiles_n)), block(NTHREADS);
-    const bool wb = a->B_bf16 != nullptr;
-    if (wb) GAD_CHECK(gad_aligned16(a->B_bf16) && a->ldb % 8 == 0, "gad_gemm: B_bf16 must be 16-byte aligned with ldb %% 8 == 0");
-    d.Bh = (const unsigned short*)a->B_bf16;
-#define GAD_PATCH_BF16(W_, NI_)                                                                           \
-    do {                                                                                                  \
-      if (wb) hipLaunchKernelGGL((conv3x3_patch_bf16_kernel<W_, NI_, true>), grid, block, 0, st, d);      \
-      else hipLaunchKernelGGL((conv3x3_patch_bf16_kernel<W_, NI_, false>), grid, block, 0, st, d);        \
-    } while (0)
-    if (a->g.Wo == 64) GAD_PATCH_BF16(64, 1);
-    else if (a->g.Wo == 32) GAD_PATCH_BF16(32, 1);
-    else if (a->g.Wo == 16) GAD_PATCH_BF16(16, 1);
-    else if (a->g.Wo == 8) GAD_PATCH_BF16(8, 2);
-    else GAD_PATCH_BF16(4, 8);
+  return 0;
+}
+
+static int launch_patch_bf16(const Route& r, DevArgs& d, hipStream_t st) {
+  const gad_gemm_args* a = &r.a;
+  d.tiles_m = (int)gad_ceil_div(a->M, 128);
+  d.tiles_n = (int)gad_ceil_div(a->N, 128);
+  d.splitk = 1;
+  dim3 grid((unsigned)(d.tiles_m * d.tiles_n)), block(NTHREADS);
+  const bool wb = a->B_bf16 != nullptr;
+  if (wb) GAD_CHECK(gad_aligned16(a->B_bf16) && a->ldb % 8 == 0, "gad_gemm: B_bf16 must be 16-byte aligned with ldb %% 8 == 0");
+  d.Bh = (const unsigned short*)a->B_bf16;
+#define GAD_PATCH_BF16(W_, NI_)                                                                         \
+  do {                                                                                                  \
+    if (wb) hipLaunchKernelGGL((conv3x3_patch_bf16_kernel<W_, NI_, true>), grid, block, 0, st, d);      \
+    else hipLaunchKernelGGL((conv3x3_patch_bf16_kernel<W_, NI_, false>), grid, block, 0, st, d);        \
+  } while (0)
+  if (a->g.Wo == 64) GAD_PATCH_BF16(64, 1);
+  else if (a->g.Wo == 32) GAD_PATCH_BF16(32, 1);
+  else if (a->g.Wo == 16) GAD_PATCH_BF16(16, 1);
+  else if (a->g.Wo == 8) GAD_PATCH_BF16(8, 2);
+  else GAD_PATCH_BF16(4, 8);
 #undef GAD_PATCH_BF16
-    GAD_LAUNCH_CHECK("gad_gemm(conv3x3 patch)");
-    return 0;
+  GAD_LAUNCH_CHECK("gad_gemm(conv3x3 patch)");
+  return 0;
+}
+
+static int launch_patch_f32(const Route& r, DevArgs& d, hipStream_t st) {
+  const gad_gemm_args* a = &r.a;
+  const PatchPlan& pp = r.pp;
+  d.tiles_m = (int)gad_ceil_div(a->M, 128);
+  d.tiles_n = (int)gad_ceil_div(a->N, pp.bn);
+  d.splitk = pp.splitk;
+  d.ktiles_per_split = pp.chunks_per_split;
+  if (pp.splitk > 1) {
+    int64_t need = (int64_t)pp.splitk * a->M * a->N * (int64_t)sizeof(float);
+    GAD_CHECK(a->ws && a->ws_bytes >= need, "gad_gemm: patch-conv split-K workspace too small (%lld < %lld)", (long long)a->ws_bytes, (long long)need);
   }
-  PatchPlan pp;
-  if (use_patch_conv_f32(a, &pp)) {
-    d.tiles_m = (int)gad_ceil_div(a->M, 128);
-    d.tiles_n = (int)gad_ceil_div(a->N, pp.bn);
-    d.splitk = pp.splitk;
-    d.ktiles_per_split = pp.chunks_per_split;
-    if (pp.splitk > 1) {
-      int64_t need = (int64_t)pp.splitk * a->M * a->N * (int64_t)sizeof(float);
-      GAD_CHECK(a->ws && a->ws_bytes >= need, "gad_gemm: patch-conv split-K workspace too small (%lld < %lld)", (long long)a->ws_bytes, (long long)need);
-    }
-    dim3 grid((unsigned)pp.blocks), block(NTHREADS);
-    const bool dg = am == GAD_A_CONVT;
-#define GAD_PATCH(W_, NI_)                                                                                      \
-    do {                                                                                                        \
-      if (dg) hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, true>), grid, block, 0, st, d);             \
-      else if (pp.bn == 96) hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, false, 96>), grid, block, 0, st, d);   \
-      else if (pp.bn == 160) hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, false, 160>), grid, block, 0, st, d); \
-      else hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, false>), grid, block, 0, st, d);               \
-    } while (0)
-    if (a->g.Wo == 64) GAD_PATCH(64, 1);
-    else if (a->g.Wo == 32) GAD_PATCH(32, 1);
-    else if (a->g.Wo == 16) GAD_PATCH(16, 1);
-    else if (a->g.Wo == 8) GAD_PATCH(8, 2);
-    else GAD_PATCH(4, 8);
+  dim3 grid((unsigned)pp.blocks), block(NTHREADS);
+  const bool dg = a->a_mode == GAD_A_CONVT;
+#define GAD_PATCH(W_, NI_)                                                                                           \
+  do {                                                                                                               \
+    if (dg) hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, true>), grid, block, 0, st, d);                    \
+    else if (pp.bn == 96) hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, false, 96>), grid, block, 0, st, d);   \
+    else if (pp.bn == 160) hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, false, 160>), grid, block, 0, st, d); \
+    else hipLaunchKernelGGL((conv3x3_patch_f32_kernel<W_, NI_, false>), grid, block, 0, st, d);                      \
+  } while (0)
+  if (a->g.Wo == 64) GAD_PATCH(64, 1);
+  else if (a->g.Wo == 32) GAD_PATCH(32, 1);
+  else if (a->g.Wo == 16) GAD_PATCH(16, 1);
+  else if (a->g.Wo == 8) GAD_PATCH(8, 2);
+  else GAD_PATCH(4, 8);
 #undef GAD_PATCH
-    GAD_LAUNCH_CHECK("gad_gemm(conv3x3 patch f32)");
-    if (pp.splitk > 1) {
-      launch_splitk_reduce(d, 1, st);
-      GAD_LAUNCH_CHECK("gad_gemm(patch splitk reduce)");
-    }
-    return 0;
+  GAD_LAUNCH_CHECK("gad_gemm(conv3x3 patch f32)");
+  if (pp.splitk > 1) {
+    launch_splitk_reduce(d, 1, st);
+    GAD_LAUNCH_CHECK("gad_gemm(patch splitk reduce)");
   }
-  // generic engine: the one place the tile / split-K cost model runs
-  const Plan pl = make_plan(a);
+  return 0;
+}
+
+// the generic engine: the one place the tile / split-K cost model (make_plan) runs
+static int launch_engine(const Route& r, DevArgs& d, hipStream_t st) {
+  const gad_gemm_args* a = &r.a;
+  const Plan& pl = r.plan;
+  const int am = a->a_mode, bmode = a->b_mode, vec = r.vec;
+  const bool bf16 = r.bf16;
+  const long batch = a->batch > 0 ? a->batch : 1;
   GAD_CHECK(pl.nblocks > 0 && pl.nblocks < (1L << 31), "gad_gemm: grid too large");
   if (pl.splitk > 1) {
     int64_t need = (int64_t)batch * pl.splitk * a->M * a->N * (int64_t)sizeof(float);
@@ -3324,7 +3354,7 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
   if (a->A2) {
     if (bf16) launch_bf16<A_CONV2, GAD_B_KC>(d, pl, st);
     else launch_mode<A_CONV2, GAD_B_KC, 4>(d, pl, st);
-  } else if (ksplit2) {
+  } else if (a->A_k2) {
     const bool lean = vec == 4 && a->K % BK == 0 && a->k_split % BK == 0 && !(a->flags & GAD_GEMM_GENERAL_LOADERS);
     if (bmode == GAD_B_KC) {
       if (bf16 && lean) launch_bf16<A_KC2_L, B_KC2_L>(d, pl, st);
@@ -3374,4 +3404,30 @@ extern "C" int gad_gemm(const gad_gemm_args* a, void* stream) {
     GAD_LAUNCH_CHECK("gad_gemm(splitk reduce)");
   }
   return 0;
+}
+
+extern "C" int gad_gemm(const gad_gemm_args* args, void* stream) {
+  GAD_CHECK(args && args->A && args->B && args->C, "gad_gemm: null pointer");
+  const gad_gemm_args canon = canonical(args);
+  if (const int rc = check_args(&canon)) return rc;
+  const Route r = route_of(&canon);
+  if (const int rc = check_stage_flags(r)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  DevArgs d = dev_args(&r.a);
+  switch (r.kind) {
+    case RouteKind::SPLIT_N: case RouteKind::SPLIT_M: {
+      gad_gemm_args lo, hi;
+      split_halves(r, &lo, &hi);
+      const int rc = gad_gemm(&lo, stream);
+      return rc ? rc : gad_gemm(&hi, stream);
+    }
+    case RouteKind::WINO_WGRAD: return launch_wino_wgrad(r, stream);
+    case RouteKind::WINO: return launch_wino(r, d, stream);
+    case RouteKind::FEWOUT: return launch_fewout(r, d, st);
+    case RouteKind::WGRAD_PATCH: return launch_wgrad_patch(r, d, st);
+    case RouteKind::PATCH_BF16: return launch_patch_bf16(r, d, st);
+    case RouteKind::PATCH_F32: return launch_patch_f32(r, d, st);
+    case RouteKind::ENGINE: return launch_engine(r, d, st);
+  }
+  return 1;
 }

@@ -336,8 +336,6 @@ class GemmProfiler:
             check(lib.gad_gemm(C.byref(a), _stream()), "gad_gemm")
         e.record()
         name = self.NAMES.get((a.a_mode, a.b_mode), "gemm") + ("", "_bf16", f"_patch_w{a.g.Wo}", f"_patch_bf16_w{a.g.Wo}", f"_fewout_valu_w{a.g.Wo}", "_wino", "_wino4", "_wino4")[kid]   # (the Winograd kernels are one instance for every map width)
-        if kid == 3:                         # bf16 patch kernel: fixed 128 x 128 tiles
-            tile.value, sk.value = 128, 1
         key = (name, tile.value, sk.value, vec.value)
         # algorithmic bytes: every operand once (gathered tensor, not its im2col expansion) + the output
         g = a.g

@@ -148,15 +148,20 @@ enum gad_gemm_flags {
   /* Stages of a Winograd forward launch, so that a caller can put an event between them (bench.py's per-stage roofline) or
    * supply the transformed input itself: ONLY_INPUT runs the input transform x -> V into wino_ws and returns; SKIP_INPUT
    * takes wino_ws as already holding V (written by an ONLY_INPUT call with the same arguments) and runs the rest.  The two
-   * calls back to back are the same kernels in the same order as one plain call: bit-identical. */
+   * calls back to back are the same kernels in the same order as one plain call: bit-identical.  Both are refused (gad_gemm
+   * returns non-zero, nothing launched) off their route: ONLY_INPUT unless the launch takes the F(2x2) / F(4x4) forward route
+   * (gad_gemm_kernel_id 5 / 6), SKIP_INPUT unless it takes one of those or the Winograd weight gradient (7). */
   GAD_GEMM_WINO_ONLY_INPUT = 64,
   GAD_GEMM_WINO_SKIP_INPUT = 128
 };
 
 int64_t gad_gemm_workspace_bytes(const gad_gemm_args* a);
-/* which kernel instance gad_gemm would launch: row extent of the block tile (128 or 64 for the generic engine - 128 also
- * stands for its 128 x 64 form -, the channel tile 96 / 128 / 160 for the fp32 patch forward, 256 pixels for the vector-ALU
- * conv_out kernel), split-K factor, vector width (4 or 1) */
+/* which kernel instance gad_gemm would launch: tile, split-K factor, vector width (4 or 1).  tile by route: generic engine
+ * 128 or 64 (128 also stands for its 128 x 64 form), split-K as planned; fp32 patch forward / data gradient the channel tile
+ * 96 / 128 / 160, split-K over channel chunks; patch weight gradient the output-channel tile 128 / 96 / 64 / 32, split =
+ * pixel splits; the two-launch N and M splits 224 (split: that of the single launch they replace); bf16 patch 128, split 1;
+ * vector-ALU conv_out 256 pixels, split 1; Winograd F(2x2) the channel tile, F(4x4) 128 (one-launch form: its block's tile
+ * extent 32 / 64 / 65), Winograd weight gradient 128 - split 1 for all three (the form's, not its sub-launch's) */
 int gad_gemm_plan(const gad_gemm_args* a, int32_t* tile, int32_t* splitk, int32_t* vec);
 int gad_gemm(const gad_gemm_args* a, void* stream);
 int gad_gemm_uses_bf16(const gad_gemm_args* a);   /* 1 if gad_gemm(a) would multiply bf16-rounded operands */

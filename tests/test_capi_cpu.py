@@ -192,3 +192,181 @@ def test_half_path_host_side_checks_and_planner_without_gpu():
     assert plan(65536, 256, 320) == (8, 1)                         # LoRA rank products: 128 x 128, four workgroups per CU
     assert plan(4096, 1280, 1280) == (9, 1)                        # 16x16 level Linear: more 128 x 128 tiles than 128 x 320 ones
     assert plan(65536, 4, 2880, conv=True)[0] in (1, 8, 9)         # conv_out
+
+
+# ---- gad_gemm's route table: the five host queries over a fixed grid of launches, against tests/golden/gemm_routes.npz ----
+ROUTE_COLUMNS = ("kernel_id", "tile", "splitk", "vec", "ws_bytes", "wino_bytes", "uses_bf16")
+_P = 1 << 24                          # placeholder addresses: the queries read only their 16-byte alignment
+
+
+def _route_args(a_mode, b_mode, M, N, K, geom=None, batch=1):
+    a = _capi.GemmArgs()
+    a.A, a.B, a.C = _P, 2 * _P, 3 * _P
+    a.a_mode, a.b_mode, a.M, a.N, a.K, a.batch, a.alpha = a_mode, b_mode, M, N, K, batch, 1.0
+    a.lda = M if a_mode == _capi.A_MC else (geom[2] if a_mode == _capi.A_CONV else K)
+    a.ldb = N if b_mode == _capi.B_MC else K
+    a.ldc = N
+    if geom is not None:
+        H, W, C, Ho, Wo, k, stride, pad, ups = geom
+        a.g = _capi.ConvGeom(H, W, C, C, Ho, Wo, k, k, stride, pad, pad, ups)
+    return a
+
+
+def _set(**kw):
+    def f(a):
+        for k, v in kw.items():
+            setattr(a, k, v)
+    return f
+
+
+def _ragged(a):                       # leading dimensions that break the float4 path
+    a.lda += 1
+    a.ldb += 1
+    a.g.ldx = a.g.C + 1
+
+
+def _epilogue(a):
+    a.bias, a.residual, a.ldr = 4 * _P, 5 * _P, a.N
+    a.rowadd, a.ld_rowadd, a.rows_per_group = 6 * _P, a.N, max(1, a.g.Ho * a.g.Wo)
+
+
+def _split_m_hint(a):                 # forced weight-gradient row split: 128-channel tiles, then the rest
+    a.tile_hint = 1000 + (a.M // 2 // 128 * 128 or 128)
+
+
+F = _capi
+WINO = dict(B_wino=7 * _P, B_wino4=8 * _P)
+ROUTE_VARIANTS = [
+    _set(operand_precision=1), _set(**WINO), _set(B_wino=7 * _P), _set(B_wino4=8 * _P),
+    _set(flags=F.GEMM_NO_PATCH, **WINO), _set(flags=F.GEMM_TAP_MAJOR_K, **WINO), _set(flags=F.GEMM_SCALAR_EPILOGUE, **WINO),
+    _set(flags=F.GEMM_GENERAL_LOADERS, **WINO), _set(flags=F.GEMM_NO_WINO, **WINO), _set(flags=F.GEMM_WINO_WGRAD),
+    _set(flags=F.GEMM_WINO_WGRAD, tile_hint=8), _set(flags=F.GEMM_WINO_ONLY_INPUT, **WINO),
+    _set(flags=F.GEMM_WINO_SKIP_INPUT, B_wino4=8 * _P), _set(flags=F.GEMM_WINO_WGRAD | F.GEMM_WINO_SKIP_INPUT, B_wino4=8 * _P),
+    *[_set(tile_hint=t, **WINO) for t in range(1, 12)], _split_m_hint,
+    _set(splitk_hint=1), _set(splitk_hint=2), _set(splitk_hint=5), _set(operand_precision=1, tile_hint=2),
+    _epilogue, _set(residual=5 * _P, ldr=0, **WINO), _ragged, _set(C=3 * _P + 4, **WINO), _set(A=_P + 4, flags=F.GEMM_WINO_WGRAD),
+    _set(operand_precision=1, flags=F.GEMM_NO_PATCH), _set(alpha=0.5, flags=F.GEMM_WINO_WGRAD),
+]
+
+
+def gemm_route_grid():
+    """The deterministic grid of gad_gemm_args the route table is recorded on: every mode pair over maps 4..64 (odd, upsampled,
+    stride 2, 1x1), channel counts 3..640, batches 1..1024; each shape plain, with bf16 operands, with its Winograd inputs and
+    with a rotating pick of ROUTE_VARIANTS (switches, tile / split hints, epilogues, ragged or misaligned operands)."""
+    geoms = [(s, s, s, s, 3, 1, 1, 0) for s in (4, 8, 16, 32, 64)] + [(s // 2, s // 2, s, s, 3, 1, 1, 1) for s in (8, 16, 32, 64)]
+    geoms += [(s, s, s // 2, s // 2, 3, 2, 1, 0) for s in (8, 32, 64)] + [(7, 7, 7, 7, 3, 1, 1, 0), (12, 16, 12, 16, 3, 1, 1, 0)]
+    geoms += [(s, s, s, s, 1, 1, 0, 0) for s in (8, 32)]
+    chans = (3, 4, 32, 96, 128, 224, 256, 320, 448, 640)
+    couts = (3, 4, 64, 96, 128, 224, 320, 448, 672)
+    batches = (1, 2, 8, 64, 256, 1024)
+    i = 0
+
+    def emit(base, *extra):
+        nonlocal i
+        i += 1
+        yield base()
+        for v in [*extra] + [ROUTE_VARIANTS[(i * 7 + j * 13) % len(ROUTE_VARIANTS)] for j in range(3)]:
+            a = base()
+            v(a)
+            yield a
+    for gi, (H, W, Ho, Wo, k, s, p, u) in enumerate(geoms):
+        for ci, C in enumerate(chans):
+            for ni, N in enumerate(couts):
+                B = batches[(gi + ci + ni) % len(batches)]
+                B2 = batches[(gi + 2 * ci + 3 * ni + 1) % len(batches)]
+                geom = (H, W, C, Ho, Wo, k, s, p, u)
+                yield from emit(lambda: _route_args(F.A_CONV, F.B_KC, B * Ho * Wo, N, k * k * C, geom), _set(**WINO), _set(operand_precision=1))
+                yield from emit(lambda: _route_args(F.A_CONV, F.B_KC, B2 * Ho * Wo, N, k * k * C, geom), _set(**WINO), _set(operand_precision=1))
+                yield from emit(lambda: _route_args(F.A_CONVT, F.B_WDGRAD, B2 * Ho * Wo, N, k * k * C, geom), _set(operand_precision=1))
+                yield from emit(lambda: _route_args(F.A_MC, F.B_CONV, N, k * k * C, B * Ho * Wo, geom), _set(flags=F.GEMM_WINO_WGRAD))
+                yield from emit(lambda: _route_args(F.A_MC, F.B_CONV, N, k * k * C, B2 * Ho * Wo, geom), _set(flags=F.GEMM_WINO_WGRAD))
+    for pair in ((F.A_KC, F.B_KC), (F.A_KC, F.B_MC), (F.A_MC, F.B_MC)):
+        for M in (1, 7, 64, 256, 1000, 4096, 16384, 65536, 262144):
+            for N in (3, 4, 64, 96, 128, 320, 640, 1280):
+                for K in (4, 27, 32, 256, 320, 640, 2560):
+                    for batch in (1, 36):
+                        yield from emit(lambda: _route_args(*pair, M, N, K, batch=batch), _set(operand_precision=1))
+    for M in (1024, 16384, 65536):    # two-source gathers (3x3 and 1x1) and the K-concatenated dense form
+        for C1, C in ((128, 256), (256, 384), (320, 640), (96, 200)):
+            for k in (1, 3):
+                s = int((M // 4) ** 0.5)
+                def two(k=k, C=C, C1=C1, s=s):
+                    a = _route_args(F.A_CONV, F.B_KC, M, 320, k * k * C, (s, s, C, s, s, k, 1, k // 2, 0))
+                    a.A2, a.a_split, a.ldx2, a.g.ldx = 9 * _P, C1, C - C1, C1
+                    return a
+                yield from emit(two, _set(operand_precision=1))
+            def cat(C=C, C1=C1):
+                a = _route_args(F.A_KC, F.B_KC, M, 320, C)
+                a.lda, a.A_k2, a.B_k2, a.k_split, a.lda_k2, a.ldb_k2 = C1, 9 * _P, 10 * _P, C1, C - C1, C - C1
+                return a
+            yield from emit(cat, _set(operand_precision=1))
+
+
+def gemm_route_table(lib):
+    """The five route queries of every grid case, as int64 columns (ROUTE_COLUMNS) plus the cases' mode pairs."""
+    rows, modes = [], []
+    tile, sk, vec = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    for a in gemm_route_grid():
+        r = ctypes.byref(a)
+        assert lib.gad_gemm_plan(r, ctypes.byref(tile), ctypes.byref(sk), ctypes.byref(vec)) == 0
+        rows.append((lib.gad_gemm_kernel_id(r), tile.value, sk.value, vec.value, lib.gad_gemm_workspace_bytes(r),
+                     lib.gad_gemm_wino_bytes(r), lib.gad_gemm_uses_bf16(r)))
+        modes.append((a.a_mode, a.b_mode))
+    import numpy as np
+    cols = np.array(rows, dtype=np.int64).T
+    return dict(zip(ROUTE_COLUMNS, cols)), np.array(modes, dtype=np.int64)
+
+
+def test_gemm_route_table_matches_the_recorded_one(golden_dir):
+    """Every size query of gad_gemm reads the one route route_of resolves: kernel id, plan, workspace and Winograd bytes and
+    the bf16 answer over the grid are the ones recorded from the library before that refactor (tests/golden/gemm_routes.npz).
+    The one deliberate change: the bf16 LDS-patch route (kernel id 3) reports what it launches - 128 x 128 tiles, no split,
+    no workspace - where the old planner reported the generic engine's plan."""
+    import numpy as np
+    want = dict(np.load(os.path.join(golden_dir, "gemm_routes.npz")))
+    got, modes = gemm_route_table(_capi.load())
+    kid = want["kernel_id"]
+    assert len(got["kernel_id"]) == len(kid)
+    patch_bf16 = kid == 3
+    want["tile"][patch_bf16], want["splitk"][patch_bf16], want["ws_bytes"][patch_bf16] = 128, 1, 0
+    for c in ROUTE_COLUMNS:
+        bad = np.nonzero(got[c] != want[c])[0]
+        assert len(bad) == 0, f"{c}: {len(bad)} cases differ, first {bad[:5].tolist()}: {got[c][bad[:5]].tolist()} != {want[c][bad[:5]].tolist()}"
+    # what the grid covers
+    fwd, wgrad = (modes[:, 0] == _capi.A_CONV) | (modes[:, 0] == _capi.A_CONVT), modes[:, 1] == _capi.B_CONV
+    tile, ws = got["tile"], got["ws_bytes"]
+    assert set(range(8)) <= set(kid.tolist())
+    assert ((kid == 2) & (tile == 224) & fwd).any() and ((kid == 2) & (tile == 224) & wgrad).any()     # split-N, split-M
+    assert ((kid == 6) & (tile == 65)).any()                                                           # narrow one-launch F(4x4)
+    assert (got["vec"] == 1).any()
+    assert (((kid == 0) | (kid == 1)) & (ws > 0)).any()                                                # generic split-K
+    assert ((kid == 2) & fwd & (ws > 0)).any() and ((kid == 2) & wgrad & (ws > 0)).any()               # patch split-K, patch wgrad
+    assert ((kid == 6) & (ws > 0)).any()                                                               # three-launch F(4x4)
+
+
+def test_winograd_stage_flags_are_refused_off_their_route():
+    """GAD_GEMM_WINO_ONLY_INPUT / _SKIP_INPUT run one stage of a Winograd launch.  A launch routed anywhere else would run a
+    direct kernel that reads A (which the caller may hold only as the transformed image): gad_gemm refuses it on the host."""
+    lib = _capi.load()
+    kid = lambda a: lib.gad_gemm_kernel_id(ctypes.byref(a))     # noqa: E731
+
+    def refused(a, flag):
+        return lib.gad_gemm(ctypes.byref(a), None) != 0 and flag.encode() in lib.gad_last_error()
+    conv = _route_args(_capi.A_CONV, _capi.B_KC, 512 * 32 * 32, 128, 9 * 128, (32, 32, 128, 32, 32, 3, 1, 1, 0))
+    conv.B_wino4 = 8 * _P
+    conv.flags = _capi.GEMM_WINO_SKIP_INPUT
+    assert kid(conv) == 6
+    conv.flags |= _capi.GEMM_NO_WINO                                          # the same convolution routed direct
+    assert kid(conv) == 2 and refused(conv, "GAD_GEMM_WINO_SKIP_INPUT")
+    small = _route_args(_capi.A_CONV, _capi.B_KC, 2 * 8 * 8, 128, 9 * 128, (8, 8, 128, 8, 8, 3, 1, 1, 0))
+    small.B_wino4, small.flags = 8 * _P, _capi.GEMM_WINO_SKIP_INPUT          # too small for Winograd: the planner stays direct
+    assert kid(small) not in (5, 6) and refused(small, "GAD_GEMM_WINO_SKIP_INPUT")
+    split = _route_args(_capi.A_CONV, _capi.B_KC, 64 * 32 * 32, 448, 9 * 224, (32, 32, 224, 32, 32, 3, 1, 1, 0))
+    tile, sk, vec = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    assert lib.gad_gemm_plan(ctypes.byref(split), ctypes.byref(tile), ctypes.byref(sk), ctypes.byref(vec)) == 0
+    assert tile.value == 224                                                  # the two launches over 128- / 96-wide tiles
+    split.flags = _capi.GEMM_WINO_SKIP_INPUT
+    assert refused(split, "GAD_GEMM_WINO_SKIP_INPUT")
+    wg = _route_args(_capi.A_MC, _capi.B_CONV, 128, 9 * 128, 128 * 32 * 32, (32, 32, 128, 32, 32, 3, 1, 1, 0))
+    wg.flags = _capi.GEMM_WINO_WGRAD | _capi.GEMM_WINO_ONLY_INPUT
+    assert kid(wg) == 7 and refused(wg, "GAD_GEMM_WINO_ONLY_INPUT")
