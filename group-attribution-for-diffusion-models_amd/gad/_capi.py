@@ -88,6 +88,15 @@ class AdamArgs(C.Structure):
                 ("weight_decay", C.c_float), ("adamw", C.c_int32), ("step", C.c_int32), ("ema_decay", C.c_float)]
 
 
+class JLArgs(C.Structure):
+    """gad_jl_args (include/gad.h): random projection of gradient rows (TRAK / D-TRAK features)"""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("G", C.c_int32), ("P", C.c_int64), ("p0", C.c_int64),
+                ("d", C.c_int32), ("seed", C.c_uint32), ("model_id", C.c_uint32), ("type", C.c_int32),
+                ("accumulate", C.c_int32), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+JL_NORMAL, JL_RADEMACHER = 0, 1
+
 GEMM_NO_PATCH, GEMM_TAP_MAJOR_K, GEMM_SCALAR_EPILOGUE, GEMM_GENERAL_LOADERS, GN_TWO_PASS = 1, 2, 4, 8, 1
 GEMM_NO_WINO = 16
 GEMM_WINO_WGRAD = 32
@@ -165,6 +174,9 @@ SIGNATURES = {
     "gad_h_upsample2x_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "gad_h_attention_fwd": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
     "gad_h_attention_bwd": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
+    # random projection (csrc/projector.hip)
+    "gad_jl_project_workspace_bytes": (_i64, [C.POINTER(JLArgs)]),
+    "gad_jl_project": (C.c_int, [C.POINTER(JLArgs), _vp]),
 }
 
 _lib = None

@@ -1,0 +1,214 @@
+"""TRAK / D-TRAK gradient features (reference src/attributions/methods/d_trak_grad.py) on the MI355X engine.
+
+`Projector` takes the constructor keys of trak.projectors.CudaProjector (fast_jl, CUDA only) and projects with
+gad_jl_project (csrc/projector.hip), which generates the random matrix on the fly.  `gradient_features` computes the
+per-sample feature of one image, emb = (1/k) sum_t grad_theta f(x, t), as ONE forward / backward of the fused engine
+over the batch of that image's k (noisy, t) rows: the gradient of the batch-mean loss is exactly that average, and it
+lands in the model's flat gradient buffer (training.flatten_params), which is staged row by row and projected.
+
+The row index of R is the offset in the flat buffer: conv weights sit in their [Cout][KH][KW][Cin] storage order and
+every parameter slot is padded to 8 floats with zeros, so R differs from the reference's vectorisation by a fixed
+permutation of rows (and the zero padding contributes nothing)."""
+from __future__ import annotations
+
+import ctypes as C
+from enum import Enum
+
+import torch
+
+from . import _capi, ops
+from ._capi import check
+
+
+class ProjectionType(str, Enum):
+    normal = "normal"
+    rademacher = "rademacher"
+
+
+_TYPES = {ProjectionType.normal: _capi.JL_NORMAL, ProjectionType.rademacher: _capi.JL_RADEMACHER}
+
+
+def jl_args(a, lda, G, P, d, seed, model_id=0, proj_type=ProjectionType.normal, p0=0, accumulate=False, out=None,
+            workspace=None, workspace_bytes=0) -> _capi.JLArgs:
+    """gad_jl_args from plain values / tensors (data pointers are read from tensors; ints are taken as addresses)"""
+    def ptr(x):
+        return None if x is None else (x.data_ptr() if torch.is_tensor(x) else int(x))
+    args = _capi.JLArgs()
+    args.A, args.lda, args.G, args.P, args.p0, args.d = ptr(a), lda, G, P, p0, d
+    args.seed, args.model_id = seed & 0xFFFFFFFF, model_id & 0xFFFFFFFF
+    args.type, args.accumulate = _TYPES[ProjectionType(proj_type)], int(bool(accumulate))
+    args.out, args.workspace, args.workspace_bytes = ptr(out), ptr(workspace), workspace_bytes
+    return args
+
+
+def workspace_bytes(G, P, d, proj_type=ProjectionType.normal) -> int:
+    n = _capi.load().gad_jl_project_workspace_bytes(C.byref(jl_args(None, (P + 3) // 4 * 4, G, P, d, 0, proj_type=proj_type)))
+    if n < 0:
+        raise _capi.GadError(f"gad_jl_project_workspace_bytes: {_capi.load().gad_last_error().decode()}")
+    return n
+
+
+def project_raw(a, out, P, seed, model_id=0, proj_type=ProjectionType.normal, p0=0, accumulate=False, workspace=None):
+    """out[G][d] (+)= a[G][:P] @ R[p0 : p0 + P] in one launch on the current stream.  `a`: fp32 device rows with a row
+    stride that is a multiple of 4; `out`: contiguous fp32 [G][d]; `workspace`: a uint8 device tensor (allocated here
+    if None)."""
+    ops._req(out, "jl out")
+    if not (a.is_cuda and a.dtype == torch.float32 and a.dim() == 2 and a.stride(1) == 1):
+        raise _capi.GadError(f"jl A: expected fp32 device rows with unit column stride, got {a.dtype} {a.device} {a.stride()}")
+    G, d = out.shape
+    if a.shape[0] != G or not 0 < P <= a.shape[1]:
+        raise _capi.GadError(f"jl: A {tuple(a.shape)} does not hold {G} rows of P={P} entries")
+    need = workspace_bytes(G, P, d, proj_type)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=out.device)
+    args = jl_args(a, a.stride(0), G, P, d, seed, model_id, proj_type, p0, accumulate, out, workspace, workspace.numel())
+    check(_capi.load().gad_jl_project(C.byref(args), ops._stream()), "gad_jl_project")
+    return out
+
+
+class Projector:
+    """Drop-in for trak.projectors.CudaProjector(grad_dim, proj_dim, seed, proj_type, device, max_batch_size).
+
+    R has unit-variance entries and no 1/sqrt(proj_dim) scale (TRAK's scores and the cosine of vanilla_gradient do not
+    change under a global scale of the features).  proj_dim must be a multiple of 64."""
+
+    def __init__(self, grad_dim, proj_dim, seed, proj_type=ProjectionType.normal, device="cuda", max_batch_size=32,
+                 *args, **kwargs):
+        self.grad_dim, self.proj_dim, self.seed = int(grad_dim), int(proj_dim), int(seed)
+        self.proj_type = ProjectionType(proj_type)
+        self.device = torch.device(device)
+        self.max_batch_size = int(max_batch_size)
+        self.workspace = torch.empty(workspace_bytes(self.max_batch_size, self.grad_dim, self.proj_dim, self.proj_type),
+                                     dtype=torch.uint8, device=self.device)
+
+    def project(self, grads, model_id, out=None, p0=0, accumulate=False):
+        """[G][grad_dim] fp32 gradient rows -> [G][proj_dim] features (rows in chunks of max_batch_size; a row's result does
+        not depend on the chunking).  `p0` / `accumulate` project a column chunk of longer rows into `out`."""
+        if grads.dim() != 2 or grads.shape[1] > self.grad_dim - p0:
+            raise ValueError(f"grads {tuple(grads.shape)}: expected [G][<= {self.grad_dim - p0}] rows")
+        if grads.dtype != torch.float32 or grads.device != self.device:
+            grads = grads.to(self.device, torch.float32)
+        P = grads.shape[1]
+        if grads.stride(1) != 1 or grads.stride(0) % 4 or grads.data_ptr() % 16:
+            padded = torch.zeros(grads.shape[0], (P + 3) // 4 * 4, device=self.device)
+            padded[:, :P] = grads
+            grads = padded
+        if out is None:
+            out = torch.empty(grads.shape[0], self.proj_dim, device=self.device)
+        for r in range(0, grads.shape[0], self.max_batch_size):
+            project_raw(grads[r:r + self.max_batch_size], out[r:r + self.max_batch_size], P, self.seed, model_id,
+                        self.proj_type, p0, accumulate, self.workspace)
+        return out
+
+
+BEHAVIOURS = ("loss", "mean-squared-l2-norm", "mean", "l1-norm", "l2-norm", "linf-norm")
+
+
+def _seed_gradient(pred, behaviour):
+    """d(mean over the k rows of f(row)) / d pred for the behaviours that are not an MSE (tiny torch ops on pred)."""
+    p = pred.detach().reshape(pred.shape[0], -1).requires_grad_(True)
+    if behaviour == "mean":
+        f = p.mean(dim=1)
+    else:
+        f = torch.linalg.vector_norm(p, ord={"l1-norm": 1, "l2-norm": 2, "linf-norm": float("inf")}[behaviour], dim=1)
+    (g,) = torch.autograd.grad(f.mean(), p)
+    return g.reshape(pred.shape).contiguous()
+
+
+class _GradStep:
+    """add_noise -> U-Net -> behaviour (+ its gradient) -> backward into the flat gradient buffer of `model`"""
+
+    def __init__(self, model, scheduler, behaviour):
+        if behaviour not in BEHAVIOURS:
+            raise NotImplementedError(f"--model_behavior {behaviour}: not ported (the engine computes {', '.join(BEHAVIOURS)})")
+        self.model, self.scheduler, self.behaviour = model, scheduler, behaviour
+        self.flat, self.gflat = model.flatten_parameters() if model._flat is None else model.flat
+        self.params = list(model.parameters())
+        self._unwritten = None
+
+    def __call__(self, x, noise, t):
+        noisy = self.scheduler.add_noise(x, noise, t)
+        pred = self.model(noisy, t).sample.contiguous()
+        if self.behaviour == "loss":                              # TRAK: MSE(pred, eps)
+            _, d = ops.mse_fwd_bwd_raw(pred, noise.contiguous())
+        elif self.behaviour == "mean-squared-l2-norm":            # D-TRAK: MSE(pred, 0)
+            _, d = ops.mse_fwd_bwd_raw(pred, torch.zeros_like(pred))
+        else:
+            d = _seed_gradient(pred, self.behaviour)
+        ops.begin_backward_step()
+        try:
+            pred.backward(d)
+        finally:
+            ops.end_backward_step()
+        if self._unwritten is None:                               # a parameter with no gradient keeps a stale slot
+            ep = ops._SINK_EPOCH[0]
+            self._unwritten = [p._gad_sink for p in self.params if getattr(p, "_gad_sink_epoch", -1) != ep]
+        for v in self._unwritten:
+            v.zero_()
+        return self.gflat
+
+
+def selected_timesteps(t_strategy, k_partition, num_train_timesteps=1000):
+    """d_trak_grad.py:625-628"""
+    if t_strategy == "uniform":
+        return list(range(0, num_train_timesteps, num_train_timesteps // k_partition))
+    if t_strategy == "cumulative":
+        return list(range(0, k_partition))
+    raise ValueError(f"t_strategy={t_strategy}")
+
+
+def gradient_features(model, scheduler, images, behaviour, timesteps, projector: Projector, opt_seed=42, batch_size=8,
+                      model_id=0, out=None):
+    """[N][proj_dim] TRAK (`loss`) / D-TRAK (`mean-squared-l2-norm`) features of `images` [N][C][H][W] (dataset order).
+
+    Noise follows the reference (d_trak_grad.py:630-638): per data batch of `batch_size` images and per t,
+    seed_everything(opt_seed * 1000 + t) and one standard-normal draw of the batch's shape on the device.  The model runs in
+    eval mode (vmap's default randomness='error' forces the same in the reference).  Rows are staged in a
+    [projector.max_batch_size][P] buffer and every full buffer is projected with one launch.  `out`: an optional host
+    array (e.g. np.memmap) that receives each projected block as it is done; the features are returned as a CPU tensor."""
+    from .coalition import seed_everything
+    dev = projector.device
+    step = _GradStep(model, scheduler, behaviour)
+    P = step.gflat.numel()
+    if P != projector.grad_dim:
+        raise ValueError(f"projector.grad_dim={projector.grad_dim} but the model's flat gradient has {P} entries")
+    was_training = model.training
+    model.eval()
+    k = len(timesteps)
+    ts = torch.tensor(list(timesteps), device=dev, dtype=torch.long)
+    N = images.shape[0]
+    feats = torch.empty(N, projector.proj_dim)
+    G = projector.max_batch_size
+    staging = torch.empty(G, P, device=dev)
+    block = torch.empty(G, projector.proj_dim, device=dev)
+    filled, row0 = 0, 0
+
+    def flush():
+        nonlocal filled, row0
+        projector.project(staging[:filled], model_id, out=block[:filled])
+        feats[row0:row0 + filled] = block[:filled].cpu()
+        if out is not None:
+            out[row0:row0 + filled] = feats[row0:row0 + filled].numpy()
+        row0 += filled
+        filled = 0
+
+    try:
+        for b0 in range(0, N, batch_size):
+            image = images[b0:b0 + batch_size].to(dev, torch.float32)
+            noises = []
+            for t in timesteps:
+                seed_everything(opt_seed * 1000 + t)
+                noises.append(torch.randn_like(image))
+            noise = torch.stack(noises, dim=1)                   # [bsz][k][C][H][W]
+            for i in range(image.shape[0]):
+                x = image[i:i + 1].expand(k, *image.shape[1:]).contiguous()
+                gflat = step(x, noise[i].contiguous(), ts)
+                staging[filled].copy_(gflat)
+                filled += 1
+                if filled == G:
+                    flush()
+        if filled:
+            flush()
+    finally:
+        model.train(was_training)
+    return feats

@@ -470,6 +470,44 @@ int gad_h_add(const void* a, const void* b, void* out, int64_t n, void* stream);
 int gad_h_attention_fwd(const gad_attention_args* a, void* stream);
 int gad_h_attention_bwd(const gad_attention_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Johnson-Lindenstrauss random projection of gradients (TRAK / D-TRAK features).
+ * Replaces trak.projectors.CudaProjector (fast_jl, CUDA only) under
+ *   src/attributions/methods/d_trak_grad.py:411-418,654.
+ *   out[g][j] = (accumulate ? out[g][j] : 0) + sum_{p<P} A[g*lda + p] * R(p0 + p, j)   g < G, j < d
+ * R is never stored: R(row, j) is a pure function of (seed, model_id, row, j, type) through
+ * Philox-4x32-10 (Random123 constants) with key (seed, model_id) and counter
+ * (column block, row low 32 bits, row high 32 bits, type):
+ *   GAD_JL_NORMAL      one call -> columns 4c..4c+3 of a row; words x -> u = fl32(fl32(x) * 2^-32 + 2^-33),
+ *                      Box-Muller on (u0,u1), (u2,u3): r = sqrt(-2 ln u_even), z_even = r cos(2 pi u_odd), z_odd = r sin(..)
+ *   GAD_JL_RADEMACHER  one call -> columns 128c..128c+127; entry j is +1 / -1 for bit (j mod 32) of word
+ *                      (j mod 128) / 32 clear / set
+ * Unit-variance entries, no 1/sqrt(d) scale.  Contraction on v_mfma_f32_16x16x4_f32 (exact fp32), split along P over a
+ * plan that depends on (P, d) only and reduced slab by slab in a fixed order: bit-reproducible, and a row's output does
+ * not depend on G or on the other rows.  A 16-B aligned with lda a multiple of 4 and >= P; d a multiple of 64; out and
+ * workspace 16-B aligned, workspace_bytes >= gad_jl_project_workspace_bytes(args).
+ * ---------------------------------------------------------------------------- */
+enum gad_jl_type { GAD_JL_NORMAL = 0, GAD_JL_RADEMACHER = 1 };
+
+typedef struct gad_jl_args {
+  const float* A;           /* [G][lda] fp32 rows to project                                  */
+  int64_t lda;              /* row stride of A in floats                                      */
+  int32_t G;                /* rows of A / out                                                */
+  int64_t P;                /* contracted length                                              */
+  int64_t p0;               /* R row of A's column 0 (projection of a chunk of a longer row) */
+  int32_t d;                /* projected dimension (columns of R and out)                     */
+  uint32_t seed, model_id;  /* Philox key                                                     */
+  int32_t type;             /* enum gad_jl_type                                               */
+  int32_t accumulate;       /* 1: out += A R, 0: out = A R                                     */
+  float* out;               /* [G][d] fp32                                                    */
+  void* workspace;          /* per-slab partials (caller owned)                               */
+  int64_t workspace_bytes;
+} gad_jl_args;
+
+/* bytes of workspace gad_jl_project needs for these arguments (-1 and gad_last_error() if they are refused) */
+int64_t gad_jl_project_workspace_bytes(const gad_jl_args* a);
+int gad_jl_project(const gad_jl_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
