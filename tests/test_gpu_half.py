@@ -152,9 +152,10 @@ def test_hconv_two_sources():
     close_h(y, _nhwc(want), extra=2e-5 * math.sqrt(9 * (C1 + C2)), what="two-source conv")
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout,k,stride,pad,ups", CONVS[:5] + CONVS[6:])
+@pytest.mark.parametrize("B,H,W,Cin,Cout,k,stride,pad,ups", CONVS)
 def test_hconv_autograd_dgrad(B, H, W, Cin, Cout, k, stride, pad, ups):
-    """HConv2dFn: data gradient through rotated / transposed weight copies (stride 1, stride 2, upsample-fused, 1x1)"""
+    """HConv2dFn: data gradient through rotated / transposed weight copies (stride 1, stride 2, upsample-fused, 1x1, and conv_out's
+    4 channels: dy and the rotated weight zero-padded to 8)"""
     from gad import ops
     x, xd = hb(rnd(B, Cin, H, W, seed=1))
     w = (rnd(Cout, Cin, k, k, seed=2, scale=0.05)).to(BF).float()
@@ -522,7 +523,7 @@ def test_hgemm_guard_bands(M, N, K, tile, sk):
         assert any(k == "ws" for k, _, _ in g.regions)
 
 
-@pytest.mark.parametrize("B,H,W,Cin,Cout,k,stride,pad,ups", CONVS[:5] + CONVS[6:])
+@pytest.mark.parametrize("B,H,W,Cin,Cout,k,stride,pad,ups", CONVS)
 def test_hconv_autograd_guard_bands(B, H, W, Cin, Cout, k, stride, pad, ups):
     from gad import ops
     x = _nhwc(rnd(B, Cin, H, W, seed=1)).to(BF).to(dev)
