@@ -62,6 +62,7 @@ struct HDev {
   int vec_out;              // the output-side operands can (the split-K reduce's epilogue)
   const u16* zero;          // the zero block (a DMA source like any other)
   int dbg_zero;             // A/B tools only (tile_hint + 100): every DMA reads the zero block - the kernel without its memory system
+  long c_seg_stride;        // hgemm_tn_kernel<true> only: floats between the outputs of consecutive segments (len1 = rows per segment)
 };
 
 // epilogue of one output element
@@ -410,6 +411,9 @@ __global__ __launch_bounds__(WM* WN * 64, (NST == 2 || WM * WN == 8) ? 2 : 1) vo
 // the 16-byte chunk index XOR-ed by (k & 7) << 1 on the DMA's source and on the read: the eight rows a 32-lane half touches then
 // fall in eight different 32-byte slots of the bank row.  128 x 128 outputs per workgroup (4 waves x 4 x 4 tiles of 16 x 16),
 // two stage buffers, fp32 output (direct, accumulating, or split-K slabs reduced by hgemm_reduce_kernel).
+// SEG (gad_hgemm_tn_seg, the per-sample LoRA gradients): blockIdx.z = s picks rows s L .. (s + 1) L - 1 of both operands and the
+// output window C + s c_seg_stride; L = p.len1 is any length, a stage's rows past the segment's end read the zero block exactly as
+// rows past K do.  Nothing else differs, so a segment's accumulation order is that of a plain launch with K = L and the same split.
 // ---------------------------------------------------------------------------------------------------------------
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
@@ -423,6 +427,7 @@ __device__ __forceinline__ bf16x8 tn_frag(const unsigned char* img, int c0) {   
   const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
   return __builtin_bit_cast(bf16x8, both);
 }
+template <bool SEG>
 __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {           // p.len1 = K (rows of A and B); p.M x p.N outputs
   constexpr int KB = 2;                                  // 32-row sub-images per stage: 64 rows of K per barrier
   constexpr int IMG = 32 * 256, OPER = KB * IMG, STAGE = 2 * OPER;
@@ -431,6 +436,9 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
   const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
   const int row0 = tile_m * 128, col0 = tile_n * 128;
   const int z = blockIdx.y;
+  const int seg = SEG ? blockIdx.z : 0;
+  const u16* const pA = SEG ? p.A + (long)seg * p.len1 * p.lda : p.A;
+  const u16* const pB = SEG ? p.B + (long)seg * p.len1 * p.ldb : p.B;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
@@ -451,8 +459,8 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
     for (int i = 0; i < NI; ++i) {
       const int kr = k0 + kr0 + 16 * i;
       const bool kin = kr < p.len1 && !p.dbg_zero;
-      const u16* sa = (kin && oka) ? p.A + ((long)(k0 + 16 * i) * p.lda + offa) : zero;
-      const u16* sb = (kin && okb) ? p.B + ((long)(k0 + 16 * i) * p.ldb + offb) : zero;
+      const u16* sa = (kin && oka) ? pA + ((long)(k0 + 16 * i) * p.lda + offa) : zero;
+      const u16* sb = (kin && okb) ? pB + ((long)(k0 + 16 * i) * p.ldb + offb) : zero;
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sa,
                                        (__attribute__((address_space(3))) void*)(dst + i * 4096), 16, 0, 0);
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sb,
@@ -490,7 +498,8 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
     __syncthreads();
   }
   // C / D of the 16 x 16 MFMA: column = lane & 15, rows 4 (lane >> 4) + register
-  float* slab = p.splitk > 1 ? p.ws + (long)z * p.M * p.N : nullptr;
+  float* slab = p.splitk > 1 ? p.ws + ((long)seg * p.splitk + z) * p.M * p.N : nullptr;
+  float* const pC = reinterpret_cast<float*>(p.C) + (SEG ? seg * p.c_seg_stride : 0L);
   const int c = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -503,7 +512,7 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
         if (m < p.M && n < p.N) {
           if (slab) slab[(long)m * p.N + n] = acc[i][j][e];
           else {
-            float* cd = reinterpret_cast<float*>(p.C) + (long)m * p.ldc + n;
+            float* cd = pC + (long)m * p.ldc + n;
             const float v = acc[i][j][e] * p.alpha;
             *cd = p.accumulate ? *cd + v : v;
           }
@@ -565,6 +574,45 @@ __global__ __launch_bounds__(256) void hgemm_reduce_kernel(const HDev p) {
   float v = 0.f;
   for (int zz = 0; zz < p.splitk; ++zz) v += p.ws[(long)zz * total + idx];
   epi_store(p, m, n, p.rowadd ? m / p.rpg : 0, v);
+}
+
+// the split reduce of hgemm_tn_kernel<true>: blockIdx.y = segment; that segment's slabs summed in slab order, alpha, (+)= into its window
+__global__ __launch_bounds__(256) void hgemm_tn_seg_reduce_kernel(const HDev p) {
+  const long total = (long)p.M * p.N;
+  const int seg = blockIdx.y;
+  const float* const ws = p.ws + (long)seg * p.splitk * total;
+  float* const pC = reinterpret_cast<float*>(p.C) + seg * p.c_seg_stride;
+  if (p.vec_out) {
+    const long idx = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 8;
+    if (idx >= total) return;
+    const int m = (int)(idx / p.N), n = (int)(idx - (long)m * p.N);
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int zz = 0; zz < p.splitk; ++zz) {
+      const float* src = ws + (long)zz * total + idx;
+      const f32x4 a0 = *reinterpret_cast<const f32x4*>(src), a1 = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { v[k] += a0[k]; v[4 + k] += a1[k]; }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) v[k] *= p.alpha;
+    float* cdst = pC + (long)m * p.ldc + n;
+    if (p.accumulate) {
+      const f32x4 c0 = *reinterpret_cast<const f32x4*>(cdst), c1 = *reinterpret_cast<const f32x4*>(cdst + 4);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { v[k] += c0[k]; v[4 + k] += c1[k]; }
+    }
+    *reinterpret_cast<f32x4*>(cdst) = f32x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f32x4*>(cdst + 4) = f32x4{v[4], v[5], v[6], v[7]};
+    return;
+  }
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int m = (int)(idx / p.N), n = (int)(idx - (long)m * p.N);
+  float v = 0.f;
+  for (int zz = 0; zz < p.splitk; ++zz) v += ws[(long)zz * total + idx];
+  v *= p.alpha;
+  float* cd = pC + (long)m * p.ldc + n;
+  *cd = p.accumulate ? *cd + v : v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1357,12 +1405,85 @@ extern "C" int gad_hgemm_tn(const gad_hgemm_args* a, void* stream) {
   d.zero = zero_block();
   GAD_CHECK(d.zero != nullptr, "gad_hgemm_tn: cannot resolve the zero block's device address");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(hgemm_tn_kernel, dim3(d.tiles_m * d.tiles_n, sk), dim3(256), 0, st, d);
+  hipLaunchKernelGGL(hgemm_tn_kernel<false>, dim3(d.tiles_m * d.tiles_n, sk), dim3(256), 0, st, d);
   GAD_LAUNCH_CHECK("hgemm_tn_kernel");
   if (sk > 1) {
     const long total = d.vec_out ? (long)a->M * a->N / 8 : (long)a->M * a->N;
     hipLaunchKernelGGL(hgemm_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d);
     GAD_LAUNCH_CHECK("hgemm_reduce_kernel");
+  }
+  return 0;
+}
+
+// ---- segmented token-axis contraction (per-sample LoRA gradients) ----
+// Row slices per segment: at least 256 rows each, at most 4 - a function of L alone (the S segments already fill the card, and the
+// workspace is S x slices x M x N floats), so a segment's bits do not depend on S.
+static int tn_seg_splitk(const gad_hgemm_seg_args* a, int* steps_out) {
+  const int steps = (a->L + 63) / 64;
+  int sk = a->splitk_hint > 0 ? a->splitk_hint : steps / 4;
+  if (a->splitk_hint <= 0 && sk > 4) sk = 4;
+  if (sk > 128) sk = 128;
+  if (sk > steps) sk = steps;
+  if (sk < 1) sk = 1;
+  const int per = (steps + sk - 1) / sk;
+  *steps_out = steps;
+  return (steps + per - 1) / per;
+}
+static int tn_seg_check(const gad_hgemm_seg_args* a, bool launch) {
+  GAD_CHECK(a && a->A && a->B && a->C, "gad_hgemm_tn_seg: null operand");
+  GAD_CHECK(a->S > 0, "gad_hgemm_tn_seg: S = %d segments (must be positive)", a->S);
+  GAD_CHECK(a->L > 0, "gad_hgemm_tn_seg: L = %d rows per segment (must be positive)", a->L);
+  GAD_CHECK(a->M > 0 && a->N > 0, "gad_hgemm_tn_seg: empty problem %d x %d", a->M, a->N);
+  GAD_CHECK(a->S <= 65535, "gad_hgemm_tn_seg: S = %d exceeds the 65535 segments of one launch", a->S);
+  GAD_CHECK((int64_t)a->S * a->L <= INT32_MAX, "gad_hgemm_tn_seg: S * L = %lld rows overflows the int32 row index",
+            (long long)a->S * a->L);
+  GAD_CHECK(a->lda % 8 == 0 && a->ldb % 8 == 0 && a->lda >= (a->M + 7) / 8 * 8 && a->ldb >= (a->N + 7) / 8 * 8,
+            "gad_hgemm_tn_seg: misaligned row strides lda = %d, ldb = %d (multiples of 8 covering M / N rounded up to 8: rows are read "
+            "in 16-byte chunks)", a->lda, a->ldb);
+  GAD_CHECK(gad_aligned16(a->A) && gad_aligned16(a->B), "gad_hgemm_tn_seg: operands must be 16-byte aligned");
+  GAD_CHECK((int64_t)a->S * a->L * (a->lda > a->ldb ? a->lda : a->ldb) < (1L << 40), "gad_hgemm_tn_seg: operand too large");
+  GAD_CHECK(a->ldc >= a->N, "gad_hgemm_tn_seg: ldc < N");
+  GAD_CHECK(a->c_seg_stride >= (int64_t)(a->M - 1) * a->ldc + a->N,
+            "gad_hgemm_tn_seg: c_seg_stride = %lld < (M - 1) * ldc + N = %lld (segment outputs would overlap)", (long long)a->c_seg_stride,
+            (long long)((int64_t)(a->M - 1) * a->ldc + a->N));
+  if (launch) {
+    int steps;
+    const int sk = tn_seg_splitk(a, &steps);
+    const int64_t need = sk > 1 ? (int64_t)a->S * sk * a->M * a->N * 4 : 0;
+    GAD_CHECK(need == 0 || (a->ws && a->ws_bytes >= need), "gad_hgemm_tn_seg: workspace too small (%lld bytes, %lld needed)",
+              (long long)(a->ws ? a->ws_bytes : 0), (long long)need);
+  }
+  return 0;
+}
+extern "C" int64_t gad_hgemm_tn_seg_workspace_bytes(const gad_hgemm_seg_args* a) {
+  if (tn_seg_check(a, false)) return -1;
+  int steps;
+  const int sk = tn_seg_splitk(a, &steps);
+  return sk > 1 ? (int64_t)a->S * sk * a->M * a->N * 4 : 0;
+}
+extern "C" int gad_hgemm_tn_seg(const gad_hgemm_seg_args* a, void* stream) {
+  if (tn_seg_check(a, true)) return 1;
+  int steps;
+  const int sk = tn_seg_splitk(a, &steps);
+  HDev d{};
+  d.A = (const u16*)a->A; d.B = (const u16*)a->B;
+  d.M = a->M; d.N = a->N; d.lda = a->lda; d.ldb = a->ldb; d.len1 = a->L;
+  d.alpha = a->alpha; d.C = a->C; d.ldc = a->ldc; d.out_f32 = 1; d.accumulate = a->accumulate;
+  d.c_seg_stride = a->c_seg_stride;
+  d.ws = (float*)a->ws;
+  d.tiles_m = (a->M + 127) / 128; d.tiles_n = (a->N + 127) / 128; d.splitk = sk; d.steps = steps;
+  d.steps_per_split = (steps + sk - 1) / sk;
+  d.vec_out = a->N % 8 == 0 && gad_aligned16(a->C) && a->ldc % 4 == 0 && a->c_seg_stride % 4 == 0 && (sk == 1 || gad_aligned16(a->ws));
+  d.vec = d.vec_out;
+  d.zero = zero_block();
+  GAD_CHECK(d.zero != nullptr, "gad_hgemm_tn_seg: cannot resolve the zero block's device address");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(hgemm_tn_kernel<true>, dim3(d.tiles_m * d.tiles_n, sk, a->S), dim3(256), 0, st, d);
+  GAD_LAUNCH_CHECK("hgemm_tn_kernel<seg>");
+  if (sk > 1) {
+    const long total = d.vec_out ? (long)a->M * a->N / 8 : (long)a->M * a->N;
+    hipLaunchKernelGGL(hgemm_tn_seg_reduce_kernel, dim3((unsigned)((total + 255) / 256), a->S), dim3(256), 0, st, d);
+    GAD_LAUNCH_CHECK("hgemm_tn_seg_reduce_kernel");
   }
   return 0;
 }

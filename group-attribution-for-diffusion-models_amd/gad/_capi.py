@@ -95,6 +95,14 @@ class JLArgs(C.Structure):
                 ("accumulate", C.c_int32), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class HGemmSegArgs(C.Structure):
+    """gad_hgemm_seg_args (include/gad.h): segmented token-axis contraction (per-sample LoRA gradients)"""
+    _fields_ = [("A", C.c_void_p), ("B", C.c_void_p), ("C", C.c_void_p), ("ws", C.c_void_p), ("ws_bytes", C.c_int64),
+                ("c_seg_stride", C.c_int64), ("M", C.c_int32), ("N", C.c_int32), ("L", C.c_int32), ("S", C.c_int32),
+                ("lda", C.c_int32), ("ldb", C.c_int32), ("ldc", C.c_int32), ("alpha", C.c_float), ("accumulate", C.c_int32),
+                ("splitk_hint", C.c_int32)]
+
+
 JL_NORMAL, JL_RADEMACHER = 0, 1
 
 GEMM_NO_PATCH, GEMM_TAP_MAJOR_K, GEMM_SCALAR_EPILOGUE, GEMM_GENERAL_LOADERS, GN_TWO_PASS = 1, 2, 4, 8, 1
@@ -160,6 +168,8 @@ SIGNATURES = {
     "gad_hgemm": (C.c_int, [C.POINTER(HGemmArgs), _vp]),
     "gad_hgemm_tn_workspace_bytes": (_i64, [C.POINTER(HGemmArgs)]),
     "gad_hgemm_tn": (C.c_int, [C.POINTER(HGemmArgs), _vp]),
+    "gad_hgemm_tn_seg_workspace_bytes": (_i64, [C.POINTER(HGemmSegArgs)]),
+    "gad_hgemm_tn_seg": (C.c_int, [C.POINTER(HGemmSegArgs), _vp]),
     "gad_h_transpose": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gad_h_cast": (C.c_int, [_vp, _vp, _i64, _i32, _vp]),
     "gad_h_shadow_pairs": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp]),

@@ -317,6 +317,84 @@ def wgrad_raw(dy2d, x2d, out, accumulate, alpha=1.0, splitk_hint=0):
     check(lib.gad_hgemm_tn(C.byref(a), _st()), "gad_hgemm_tn")
 
 
+def wgrad_seg_args(dy2d, x2d, out0, N, K, S, c_seg_stride, accumulate=False, alpha=1.0, splitk_hint=0, ldc=None):
+    """gad_hgemm_seg_args of out_s[N][K] (+)= alpha * dy2d[s L : (s + 1) L, :N]^T x2d[s L : (s + 1) L, :K], L = rows / S; `out0` is
+    segment 0's output (a tensor, or a device address)"""
+    rows = dy2d.shape[0]
+    if rows % S or x2d.shape[0] != rows:
+        raise _capi.GadError(f"segmented wgrad: {rows} / {x2d.shape[0]} operand rows do not split into {S} equal segments")
+    a = _capi.HGemmSegArgs()
+    a.A, a.B, a.C = dy2d.data_ptr(), x2d.data_ptr(), (out0.data_ptr() if torch.is_tensor(out0) else int(out0))
+    a.M, a.N, a.L, a.S = N, K, rows // S, S
+    a.lda, a.ldb, a.ldc, a.c_seg_stride = dy2d.stride(0), x2d.stride(0), (K if ldc is None else ldc), c_seg_stride
+    a.alpha, a.accumulate, a.splitk_hint = alpha, int(accumulate), splitk_hint
+    return a
+
+
+def wgrad_seg_raw(dy2d, x2d, out0, N, K, S, c_seg_stride, accumulate=False, alpha=1.0, splitk_hint=0, ldc=None):
+    """The per-sample LoRA parameter gradients of a batch in one launch (gad_hgemm_tn_seg): segment s of the token axis goes to
+    out0 + s * c_seg_stride (fp32)."""
+    lib = _capi.load()
+    a = wgrad_seg_args(dy2d, x2d, out0, N, K, S, c_seg_stride, accumulate, alpha, splitk_hint, ldc)
+    need = lib.gad_hgemm_tn_seg_workspace_bytes(C.byref(a))
+    if need < 0:
+        raise _capi.GadError(f"gad_hgemm_tn_seg: {lib.gad_last_error().decode()}")
+    if need:
+        ws = ops._scratch("ws", need, dy2d.device) if ops.SCRATCH_ALLOC is not None else ops.workspace(dy2d.device)
+        if ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=dy2d.device)
+        a.ws, a.ws_bytes = ws.data_ptr(), ws.numel()
+    check(lib.gad_hgemm_tn_seg(C.byref(a), _st()), "gad_hgemm_tn_seg")
+
+
+class PerSampleSink:
+    """Destination of the per-sample LoRA gradients of one backward: segment s of the batch's token axis (S equal runs of the
+    batch, in batch order) goes to staging[row0 + s][offset of the matrix in the flat gradient buffer], scaled by alpha, on top
+    of what is there if `accumulate` (the chunks of a timestep average) or if the matrix already got a gradient in this pass."""
+
+    def __init__(self, staging, row0, segments, alpha=1.0, accumulate=False):
+        if not (staging.is_cuda and staging.dtype == torch.float32 and staging.dim() == 2 and staging.stride(1) == 1
+                and staging.stride(0) % 4 == 0 and staging.data_ptr() % 16 == 0):
+            raise _capi.GadError("per-sample sink: staging must be 16-byte aligned fp32 device rows with a stride that is a multiple of 4")
+        if not 0 <= row0 <= row0 + segments <= staging.shape[0] or segments < 1:
+            raise _capi.GadError(f"per-sample sink: rows {row0} .. {row0 + segments} do not fit the {staging.shape[0]} staging rows")
+        self.staging, self.row0, self.segments, self.alpha, self.accumulate = staging, row0, segments, float(alpha), bool(accumulate)
+        self.seen = set()
+
+    def write(self, param, dy2d, x2d):
+        """param's [N][K] gradient dy2d^T x2d, one per segment"""
+        where = getattr(param, "_gad_flat", None)
+        if where is None:
+            raise _capi.GadError("per-sample sink: the parameter is not in a flat buffer (training.flatten_params)")
+        _, off, n = where
+        stride = self.staging.stride(0)
+        if off + n > self.staging.shape[1]:
+            raise _capi.GadError(f"per-sample sink: slot {off} + {n} exceeds the staging rows' {self.staging.shape[1]} entries")
+        N, K = param.shape
+        acc = self.accumulate or id(param) in self.seen
+        self.seen.add(id(param))
+        wgrad_seg_raw(dy2d, x2d, self.staging.data_ptr() + 4 * (self.row0 * stride + off), N, K, self.segments, stride,
+                      accumulate=acc, alpha=self.alpha)
+
+
+class per_sample_gradients:
+    """with per_sample_gradients(staging, row0, S, alpha, accumulate): pred.backward(d) - routes the LoRA gradients of that backward
+    into the staging rows.  The flat-buffer sink (ops.begin_backward_step) is left as it was found."""
+
+    def __init__(self, staging, row0, segments, alpha=1.0, accumulate=False):
+        self.sink = PerSampleSink(staging, row0, segments, alpha, accumulate)
+
+    def __enter__(self):
+        if ops._PER_SAMPLE[0] is not None or ops._SINK_ACTIVE[0]:
+            raise _capi.GadError("per-sample sink: another gradient sink is active")
+        ops._PER_SAMPLE[0] = self.sink
+        return self.sink
+
+    def __exit__(self, *exc):
+        ops._PER_SAMPLE[0] = None
+        return False
+
+
 # ----------------------------------------------------------------------------------
 # autograd functions
 # ----------------------------------------------------------------------------------
@@ -427,7 +505,15 @@ class HLoraLinearFn(torch.autograd.Function):
             dx = linear_raw(dy2, half_weight_t(w), A2=dmid, B2=dht).view(shp)                 # dy W + dmid A
         dd = du = None
         r, K = down.shape
-        if ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and N * K <= 1.5 * r * (N + K):
+        ps = ops._PER_SAMPLE[0]
+        if ps is not None:
+            # Per-sample mode: the two direct contractions, one segment per sample.  The wide-rank route below would need S fp32
+            # [N][K] matrices G_s and 2 S small products; the direct form is two launches whatever S is.
+            if ctx.needs_input_grad[3]:
+                ps.write(down, dmid, x2)                                                      # dmid_s^T x_s
+            if ctx.needs_input_grad[4]:
+                ps.write(up, dy2, mid)                                                        # dy_s^T mid_s
+        elif ctx.needs_input_grad[3] and ctx.needs_input_grad[4] and N * K <= 1.5 * r * (N + K):
             # Wide ranks (the reference's r = 256 on 320-wide projections): the two LoRA gradients through the FULL-weight gradient
             # G = dy^T x (fp32, [N][K]):  dB = s G A^T,  dA = s B^T G  - the same sums reassociated.  One contraction over the
             # token axis instead of two (2 M N K against 2 M r (N + K) FLOPs), one operand transpose (dy; x's is shared by the

@@ -94,8 +94,18 @@ def end_backward_step():
     _SINK_ACTIVE[0] = False
 
 
+# The per-sample sink (half.PerSampleSink, set by half.per_sample_gradients): while one is active the half-path LoRA linear writes
+# the gradient of every SAMPLE of the batch into that sample's row of a [G][P] staging buffer (gad_hgemm_tn_seg) instead of
+# the batch sum into the flat slot.  No other operator can produce per-sample gradients, so asking one for a parameter gradient
+# in this mode is an error.
+_PER_SAMPLE = [None]
+
+
 def _sink(param):
     """(destination view or None, first_write flag)"""
+    if _PER_SAMPLE[0] is not None and param is not None and param.requires_grad:
+        raise _capi.GadError("per-sample gradient sink: only the LoRA matrices of the half-precision activation path have "
+                             "per-sample gradients (csrc/half.hip: gad_hgemm_tn_seg)")
     v = getattr(param, "_gad_sink", None) if (param is not None and _SINK_ACTIVE[0]) else None
     if v is None:
         return None, True

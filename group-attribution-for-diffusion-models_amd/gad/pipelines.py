@@ -150,7 +150,9 @@ class StableDiffusionLatentPipeline:
 
     @torch.no_grad()
     def __call__(self, prompt_embeds, negative_prompt_embeds, num_inference_steps=100, guidance_scale=7.5,
-                 generator=None, height=None, width=None):
+                 generator=None, height=None, width=None, callback=None):
+        """callback(step_idx, t, latents): called after every scheduler update with the updated NCHW latents (a copy) - the
+        diffusers `callback` hook that grad_text_to_image_lora.py uses to collect the journey of a generation."""
         cfg = self.unet.config
         B = prompt_embeds.shape[0]
         hw = (height or cfg.sample_size * 8) // 8, (width or cfg.sample_size * 8) // 8
@@ -165,11 +167,13 @@ class StableDiffusionLatentPipeline:
         ctx = torch.cat([negative_prompt_embeds, prompt_embeds], 0).to(self.device, torch.float32).contiguous()
         t2 = torch.empty(2 * B, device=self.device, dtype=torch.int64)
         clip = float(sch.config.clip_sample_range) if sch.config.clip_sample else 0.0
-        for t in sch.timesteps.tolist():
+        for i, t in enumerate(sch.timesteps.tolist()):
             t2.fill_(t)
             eps = self.unet.forward_nhwc(torch.cat([x, x], 0), t2, ctx)
             a_t, a_p = sch.step_coefficients(t)
             ops.cfg_ddim_step_raw(x, eps, guidance_scale, a_t, a_p, clip, out=x)
+            if callback is not None:
+                callback(i, t, ops.nhwc_to_nchw_raw(x))
         return SimpleNamespace(latents=ops.nhwc_to_nchw_raw(x))
 
 

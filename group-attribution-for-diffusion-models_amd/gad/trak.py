@@ -8,7 +8,13 @@ lands in the model's flat gradient buffer (training.flatten_params), which is st
 
 The row index of R is the offset in the flat buffer: conv weights sit in their [Cout][KH][KW][Cin] storage order and
 every parameter slot is padded to 8 floats with zeros, so R differs from the reference's vectorisation by a fixed
-permutation of rows (and the zero padding contributes nothing)."""
+permutation of rows (and the zero padding contributes nothing).
+
+`lora_gradient_features` is the Stable-Diffusion + LoRA form (reference text_to_image/grad_text_to_image_lora.py, where
+vmap(grad(f)) yields the per-sample gradients of a batch): with bf16 activations every LoRA gradient is a contraction over
+the token axis, so ONE ordinary forward / backward over S samples x j timesteps writes all S per-sample gradients into S
+staging rows (half.per_sample_gradients -> gad_hgemm_tn_seg); with fp32 activations it runs one sample per backward
+through the flat buffer, as `gradient_features` does."""
 from __future__ import annotations
 
 import ctypes as C
@@ -211,4 +217,124 @@ def gradient_features(model, scheduler, images, behaviour, timesteps, projector:
             flush()
     finally:
         model.train(was_training)
+    return feats
+
+
+def _per_row_seed(pred, target, behaviour):
+    """d f(row) / d pred for every row of the batch (f is a mean over the row's own elements, so rows do not mix)"""
+    B = pred.shape[0]
+    if behaviour == "loss":                                       # B x the gradient of the batch-mean MSE
+        return ops.mse_fwd_bwd_raw(pred, target.contiguous(), float(B))[1]
+    if behaviour == "mean-squared-l2-norm":
+        return ops.mse_fwd_bwd_raw(pred, torch.zeros_like(pred), float(B))[1]
+    return _seed_gradient(pred, behaviour) * B
+
+
+def lora_flat_gradient(model):
+    """(LoRA parameters, their flat gradient buffer): the trainable parameters of a gad.sd.UNet2DConditionModel with injected LoRA,
+    re-homed in one flat buffer (training.flatten_params) unless a trainer already did that"""
+    from .training import flatten_params
+    params = [p for p in model.parameters() if p.requires_grad]
+    if not params or any(p.dim() != 2 for p in params):
+        raise ValueError("lora_gradient_features: the trainable parameters must be LoRA matrices (model.inject_lora / load_attn_procs)")
+    homes = {id(getattr(p, "_gad_flat", (None,))[0]) for p in params}
+    if len(homes) != 1 or getattr(params[0], "_gad_flat", None) is None:
+        flatten_params(params)
+    return params, params[0]._gad_flat[0]._gad_grad
+
+
+def lora_per_sample_gradients(model, scheduler, latents, contexts, timesteps, behaviour, rows_per_block, noise=None, seed=42,
+                              samples_per_backward=None, timesteps_per_backward=None, device=None):
+    """Generator of (first row, staging[:n]) per block of `rows_per_block` rows: staging[i] is the flat gradient
+    (1/k) sum_c grad_theta f(eps_theta(add_noise(latents[i], noise[i][c], timesteps[i][c]), timesteps[i][c], contexts[i])) over the LoRA
+    matrices theta of `model` (gad.sd.UNet2DConditionModel), f as BEHAVIOURS.  The buffer is reused by the next block.
+
+    latents [N][C][H][W], contexts [N][T][D], timesteps [N][k] (or [k]: the same for every row) - `--source train / generated`: k
+    selected timesteps of an image; `generated_journey`: k noise draws at the row's own t.  noise: [N][k][C][H][W], or None: drawn
+    per block from a device generator seeded with `seed` (so a row's noise does not depend on the route or on the two chunk
+    sizes below).
+
+    bf16 activations (ops.half_activations()): each backward carries S = samples_per_backward rows x j = timesteps_per_backward of
+    their timesteps; the average over k is accumulated over the ceil(k / j) chunks with alpha = 1 / k (gad_hgemm_tn_seg).  fp32
+    activations: one row per backward, its timesteps in chunks of j, through the flat gradient buffer."""
+    from . import half
+    if behaviour not in BEHAVIOURS:
+        raise NotImplementedError(f"--f {behaviour}: not ported (the engine computes {', '.join(BEHAVIOURS)})")
+    dev = torch.device(device) if device is not None else next(model.parameters()).device
+    params, gflat = lora_flat_gradient(model)
+    P = gflat.numel()
+    N = latents.shape[0]
+    ts_all = torch.as_tensor(timesteps, dtype=torch.long)
+    if ts_all.dim() == 1:
+        ts_all = ts_all.expand(N, -1)
+    k = ts_all.shape[1]
+    G = int(rows_per_block)
+    segmented = ops.half_activations()
+    S_max = min(int(samples_per_backward or G), G) if segmented else 1
+    j = min(int(timesteps_per_backward or (1 if segmented else k)), k)
+    was_training = model.training
+    model.eval()
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    staging = torch.zeros(G, P, device=dev)                       # slot padding and never-written slots stay zero
+    try:
+        for g0 in range(0, N, G):
+            n = min(G, N - g0)
+            x_blk = latents[g0:g0 + n].to(dev, torch.float32)
+            c_blk = contexts[g0:g0 + n].to(dev, torch.float32)
+            t_blk = ts_all[g0:g0 + n].to(dev)
+            if noise is None:
+                e_blk = torch.randn((n, k) + tuple(x_blk.shape[1:]), device=dev, generator=gen)
+            else:
+                e_blk = noise[g0:g0 + n].to(dev, torch.float32)
+            for s0 in range(0, n, S_max):
+                S = min(S_max, n - s0)
+                for c0 in range(0, k, j):
+                    jj = min(j, k - c0)
+
+                    def rep(v):
+                        return v[s0:s0 + S].unsqueeze(1).expand(S, jj, *v.shape[1:]).reshape(S * jj, *v.shape[1:]).contiguous()
+                    eps = e_blk[s0:s0 + S, c0:c0 + jj].reshape(S * jj, *x_blk.shape[1:]).contiguous()
+                    t = t_blk[s0:s0 + S, c0:c0 + jj].reshape(S * jj).contiguous()
+                    pred = model(scheduler.add_noise(rep(x_blk), eps, t), t, rep(c_blk)).sample.contiguous()
+                    d = _per_row_seed(pred, eps, behaviour)
+                    if segmented:
+                        with half.per_sample_gradients(staging, s0, S, alpha=1.0 / k, accumulate=c0 > 0):
+                            pred.backward(d)
+                        continue
+                    ops.begin_backward_step()
+                    try:
+                        pred.backward(d)                          # the flat buffer: sum over the chunk's jj rows of grad f
+                    finally:
+                        ops.end_backward_step()
+                    ep = ops._SINK_EPOCH[0]
+                    for p in params:
+                        if getattr(p, "_gad_sink_epoch", -1) != ep:
+                            p._gad_sink.zero_()
+                    if c0 == 0:
+                        torch.mul(gflat, 1.0 / k, out=staging[s0])
+                    else:
+                        staging[s0].add_(gflat, alpha=1.0 / k)
+            yield g0, staging[:n]
+    finally:
+        model.train(was_training)
+
+
+def lora_gradient_features(model, scheduler, latents, contexts, timesteps, behaviour, projector: Projector, noise=None,
+                           seed=42, samples_per_backward=None, timesteps_per_backward=None, model_id=0, out=None):
+    """[N][proj_dim] features: the rows of lora_per_sample_gradients (its arguments), each block of projector.max_batch_size rows
+    projected with one gad_jl_project launch (its workspace is 16 MiB at P = 5e7, d = 32768, G = 16: slabs x G x d floats, 8 slabs).
+    Row index of R = offset in the flat gradient buffer (module docstring).  `out`: an optional host array that receives each
+    projected block as it is done; the features are returned as a CPU tensor."""
+    _, gflat = lora_flat_gradient(model)
+    if gflat.numel() != projector.grad_dim:
+        raise ValueError(f"projector.grad_dim={projector.grad_dim} but the model's flat gradient has {gflat.numel()} entries")
+    feats = torch.empty(latents.shape[0], projector.proj_dim)
+    block = torch.empty(projector.max_batch_size, projector.proj_dim, device=projector.device)
+    for g0, rows in lora_per_sample_gradients(model, scheduler, latents, contexts, timesteps, behaviour, projector.max_batch_size,
+                                              noise, seed, samples_per_backward, timesteps_per_backward, projector.device):
+        n = rows.shape[0]
+        projector.project(rows, model_id, out=block[:n])
+        feats[g0:g0 + n] = block[:n].cpu()
+        if out is not None:
+            out[g0:g0 + n] = feats[g0:g0 + n].numpy()
     return feats

@@ -434,6 +434,29 @@ int gad_hgemm(const gad_hgemm_args* a, void* stream);
  * lda, ldb multiples of 8 and >= M, N rounded up to 8 (rows are read in 16-byte chunks; columns >= M / N feed no output); of gad_hgemm_args only A, B, C, M, N, K, lda, ldb, ldc, alpha, accumulate, ws, splitk_hint are read. */
 int64_t gad_hgemm_tn_workspace_bytes(const gad_hgemm_args* a);
 int gad_hgemm_tn(const gad_hgemm_args* a, void* stream);
+/* Segmented form of gad_hgemm_tn (per-sample LoRA gradients from one backward: the token axis of a batch is the concatenation of
+ * the samples' tokens):  C_s[m][n] (+)= alpha * sum_{k = s L .. (s + 1) L - 1} A[k][m] B[k][n],  s = 0 .. S - 1,  C_s = C + s * c_seg_stride.
+ * A, B bf16 [S * L][lda / ldb] read in place (alignment rules of gad_hgemm_tn); L is any positive length; C fp32, c_seg_stride in floats,
+ * independent of ldc and >= (M - 1) * ldc + N.  One launch covers all segments (+ one reduce launch when a segment is split along its
+ * rows).  The split depends on (M, N, L) only and the slabs are summed in slab order: a segment's result is bit-identical whatever S is
+ * and wherever the segment sits, and equals gad_hgemm_tn with K = L and the same split.  Arguments are checked before any HIP call. */
+typedef struct gad_hgemm_seg_args {
+  const void* A;            /* bf16 [S * L][lda]: column m of row k is A[k][m]                 */
+  const void* B;            /* bf16 [S * L][ldb]                                                */
+  float* C;                 /* segment 0's [M][ldc] fp32 output                                 */
+  void* ws;                 /* split workspace (caller owned)                                   */
+  int64_t ws_bytes;
+  int64_t c_seg_stride;     /* floats between the outputs of consecutive segments               */
+  int32_t M, N;             /* output rows / columns                                            */
+  int32_t L, S;             /* rows per segment, segments                                       */
+  int32_t lda, ldb, ldc;    /* row strides in elements                                          */
+  float alpha;
+  int32_t accumulate;       /* 1: C_s += result, 0: C_s = result                                */
+  int32_t splitk_hint;      /* 0 auto; > 0 force that many row slices per segment               */
+} gad_hgemm_seg_args;
+/* bytes of workspace gad_hgemm_tn_seg needs (-1 and gad_last_error() if the arguments are refused; ws / ws_bytes are not looked at) */
+int64_t gad_hgemm_tn_seg_workspace_bytes(const gad_hgemm_seg_args* a);
+int gad_hgemm_tn_seg(const gad_hgemm_seg_args* a, void* stream);
 /* dst[c][r] = bf16(src[r][c]) for `batch` matrices (strides in elements); src fp32 (src_f32 != 0) or bf16; the operand
  * transposes of the LoRA parameter gradients (dUp = dy^T mid, dDown = dmid^T x) and of the per-step bf16 shadows of the
  * LoRA matrices' transposes */
