@@ -1568,6 +1568,20 @@ static int instance_dim(int d) {
 }
 static bool exact_instance(int d) { return d > 0 && instance_dim(d) == d; }
 
+// Which forms an instance dim has (what registers and LDS allow).  route_of picks among them at run time and the dispatch
+// below instantiates exactly these, so each limit is written here and nowhere else.
+constexpr bool fwd_f32_has_nq2(int dim) { return dim <= 80; }                     // 128 queries per workgroup, fp32 operands
+constexpr bool fwd_has_wide_head(int dim) { return dim >= 160 && dim % 32 == 0; } // 8-wave split-head-dim forward
+constexpr bool bf16_has_two(int dim) { return dim <= 96; }                        // bf16 kernels: 32 rows per wave (fwd NQ = 2, bwd NU = 2)
+constexpr bool hio_instance(int dim) { return dim <= 160; }                       // bf16-storage kernels
+// single-pass backward: at most this many 64-key tiles per workgroup (dK / dV accumulators + the K / V fragments of NK key
+// tiles per wave must fit the register file); 0 = no single-pass instance
+constexpr int bwd1_max_nk(int dim) { return dim <= 40 ? 4 : dim <= 80 ? 2 : dim <= 96 ? 1 : 0; }
+// query blocks per wave of the fp32 dQ kernel of the pair (registers allow two up to d = 80, LDS-DMA form only)
+constexpr int pair_nqb(int dim, bool rg) { return dim <= 80 && !rg ? 2 : 1; }
+// does a grid of this many workgroups fill the chip twice over (two workgroups per CU in flight)?
+static bool fills_chip_twice(long workgroups) { return workgroups >= 512; }
+
 }  // namespace
 extern "C" int gad_attention_supported(int32_t d) { return d >= 1 && d <= 256; }
 namespace {
@@ -1616,46 +1630,136 @@ static dim3 grid_of(AttnDev& d, int rows, int rows_per_block) {
   return dim3((unsigned)((long)d.nblk * d.B * d.heads));
 }
 
+// ---- the router: one Route per launch ------------------------------------------------------------------------------------
+// route_of is the one place that decides the form of a launch; both queries and all four entry points read the Route it
+// returns.  Order of precedence: storage (bf16 storage: its own kernels, contract checked by check_args) > staging (a launch
+// off the float4 contract runs the RG form, always with fp32 operands) > operand type > rows per workgroup.
+enum Pass { FORWARD, BACKWARD };
+enum Io { IO_F32, IO_BF16 };              // what q / k / v / o and the gradients are stored as
+enum Ws { WS_FROM_ARGS, WS_GRANTED };     // the launch reads a->ws; the size query asks what the route would take if granted
+
+struct Route {
+  int dim = 0;              // kernel instance; 0: unsupported head dim (check_args refuses the launch)
+  bool rg = false;          // dword-staged RG form instead of LDS-DMA
+  bool bf16 = false;        // the operands are multiplied as bf16
+  bool wide_head = false;   // forward: the 8-wave split-head-dim kernel
+  int nq = 1;               // forward: 64-query blocks per workgroup
+  int nk = 0;               // backward: 64-key tiles per workgroup of the single-pass kernel; 0: the dQ + dK/dV pair
+  int nu_q = 1, nu_kv = 1;  // backward, bf16 pair: 16-row tiles per wave of the dQ and of the dK/dV kernel
+  int64_t ws_bytes = 0;     // backward: the dQ slabs of the single-pass kernel (one per key block, none for a single block)
+};
+
+// single-pass backward: keys per workgroup = 64 NK; among the NK the instance has (bwd1_max_nk) the one with the fewest padded
+// keys, ties to the larger (fewer dQ slabs: a single block writes dQ directly); 0: this launch keeps the pair
+static int bwd1_nk(int dinst, int Tk, long bh, int Tq) {
+  int best = 0;
+  long best_pad = 0;
+  for (int nk = 1; nk <= bwd1_max_nk(dinst); nk *= 2) {
+    const long nblk = gad_ceil_div(Tk, 64 * nk), pad = nblk * 64 * nk;
+    if (nk > 1 && !fills_chip_twice(bh * nblk)) continue;
+    if (!best || pad <= best_pad) { best_pad = pad; best = nk; }
+  }
+  // few keys, many queries (cross attention over 77 text tokens at 64 x 64 latents): a key block per workgroup leaves
+  // most of the chip idle, the dQ kernel of the pair is parallel over the queries - keep the pair there
+  if (best == 1 && !fills_chip_twice(bh * gad_ceil_div(Tk, 64)) && bh * gad_ceil_div(Tq, 128) > 4 * bh * gad_ceil_div(Tk, 64)) return 0;
+  return best;
+}
+
+static Route route_of(const gad_attention_args* a, Pass pass, Io io, Ws ws = WS_FROM_ARGS) {
+  Route r;
+  r.dim = gad_attention_supported(a->d) ? instance_dim(a->d) : 0;
+  r.rg = io == IO_F32 && !fast_contract(a, pass == BACKWARD);
+  r.bf16 = io == IO_BF16 || (a->operand_precision == 1 && !r.rg);
+  if (!r.dim || a->B <= 0 || a->heads <= 0 || a->Tq <= 0 || a->Tk <= 0) return r;      // (refused by check_args)
+  const long bh = (long)a->B * a->heads;
+  // 128 rows per workgroup while the (b, h, block) grid still fills the chip twice over, else 64
+  const bool two_q = fills_chip_twice(gad_ceil_div(a->Tq, 128) * bh), two_k = fills_chip_twice(gad_ceil_div(a->Tk, 128) * bh);
+  if (pass == FORWARD) {
+    if (r.rg) return r;
+    // (bf16: 64 queries per wave measured slower than 32 at d = 40, T = 4096: 731 vs 675 us)
+    if (r.bf16) r.nq = bf16_has_two(r.dim) && two_q ? 2 : 1;
+    else if (fwd_f32_has_nq2(r.dim) && two_q) r.nq = 2;
+    else r.wide_head = fwd_has_wide_head(r.dim) && !(a->flags & GAD_ATTN_NARROW_FWD);
+    return r;
+  }
+  // single-pass kernel: exact-fp32 launches up to d = 96 (flags bit 0 keeps the dQ + dK/dV pair: A/B tools, tests) whose dQ
+  // slabs fit the caller's workspace - NULL, too small or misaligned: the pair; wider heads and bf16 operands: the pair
+  if (!r.bf16 && !(a->flags & GAD_ATTN_TWO_KERNEL_BWD)) r.nk = bwd1_nk(r.dim, a->Tk, bh, a->Tq);
+  if (r.nk) {
+    const int64_t nblk = gad_ceil_div(a->Tk, 64 * r.nk);
+    const int64_t need = nblk > 1 ? nblk * a->B * a->Tq * a->heads * a->d * (int64_t)sizeof(float) : 0;
+    if (need > 0 && ws == WS_FROM_ARGS && !(a->ws && a->ws_bytes >= need && gad_aligned16(a->ws))) r.nk = 0;
+    else r.ws_bytes = need;
+  }
+  if (!r.nk && io == IO_BF16 && bf16_has_two(r.dim)) { r.nu_q = two_q ? 2 : 1; r.nu_kv = two_k ? 2 : 1; }
+  return r;
+}
+
+// ---- argument check ------------------------------------------------------------------------------------------------------
+// bf16 I/O contract: head dim an exact instance (multiple of 8, <= 160), 16-byte aligned rows (strides multiples of 8 elements)
+static int check_args(const gad_attention_args* a, Pass pass, Io io, const char* who) {
+  if (check_common(a, who)) return 1;
+  const bool h = io == IO_BF16;
+  if (h) {
+    GAD_CHECK(exact_instance(a->d) && hio_instance(a->d), "%s: head dim %d has no bf16-I/O instance", who, a->d);
+    GAD_CHECK(gad_aligned16(a->q) && gad_aligned16(a->k) && gad_aligned16(a->v) && gad_aligned16(a->o), "%s: q / k / v / o must be 16-byte aligned", who);
+    GAD_CHECK(a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->ldo % 8 == 0 && a->stride_q % 8 == 0 && a->stride_k % 8 == 0 &&
+              a->stride_v % 8 == 0 && a->stride_o % 8 == 0, "%s: strides must be multiples of 8 elements", who);
+  }
+  if (pass == FORWARD) return 0;
+  GAD_CHECK(a->lse && a->d_o && a->delta && a->dq && a->dk && a->dv, "%s: null pointer (lse / d_o / delta / dq / dk / dv)", who);
+  if (h) {
+    GAD_CHECK(gad_aligned16(a->d_o) && gad_aligned16(a->dq) && gad_aligned16(a->dk) && gad_aligned16(a->dv), "%s: gradients must be 16-byte aligned", who);
+    GAD_CHECK(a->ld_do % 8 == 0 && a->ld_dq % 8 == 0 && a->ld_dk % 8 == 0 && a->ld_dv % 8 == 0 && a->stride_do % 8 == 0 &&
+              a->stride_dq % 8 == 0 && a->stride_dk % 8 == 0 && a->stride_dv % 8 == 0, "%s: gradient strides must be multiples of 8 elements", who);
+  }
+  const int w = a->heads * a->d;
+  GAD_CHECK(a->ld_do >= w && a->ld_dq >= w && a->ld_dk >= w && a->ld_dv >= w, "%s: a gradient row stride is smaller than heads*d = %d", who, w);
+  return 0;
+}
+
+// ---- launchers: one per kernel family --------------------------------------------------------------------------------------
 template <int D, int NQ, bool RG>
-static int launch_fwd(AttnDev d, hipStream_t st) {
+static int launch_fwd(AttnDev d, hipStream_t st, const char* who) {
   static unsigned lds_set = 0;
   const int bytes = 4 * Cfg<D>::TILE * (int)sizeof(float);
-  if (set_lds(attn_fwd_f32_kernel<D, NQ, RG>, bytes, "gad_attention_fwd", &lds_set)) return 1;
+  if (set_lds(attn_fwd_f32_kernel<D, NQ, RG>, bytes, who, &lds_set)) return 1;
   const dim3 grid = grid_of(d, d.Tq, 64 * NQ);
   hipLaunchKernelGGL((attn_fwd_f32_kernel<D, NQ, RG>), grid, dim3(NT), bytes, st, d);
   return 0;
 }
 
 template <int D>
-static int launch_fwd_wide(AttnDev d, hipStream_t st) {
+static int launch_fwd_wide(AttnDev d, hipStream_t st, const char* who) {
   static unsigned lds_set = 0;
   const int bytes = (4 * Cfg<D>::TILE + 2 * 4 * 64 * 8) * (int)sizeof(float);
-  if (set_lds(attn_fwd_wide_f32_kernel<D>, bytes, "gad_attention_fwd", &lds_set)) return 1;
+  if (set_lds(attn_fwd_wide_f32_kernel<D>, bytes, who, &lds_set)) return 1;
   const dim3 grid = grid_of(d, d.Tq, 64);
   hipLaunchKernelGGL((attn_fwd_wide_f32_kernel<D>), grid, dim3(NTW), bytes, st, d);
   return 0;
 }
 
-template <int D, int NQ>
-static int launch_fwd_h(AttnDev d, hipStream_t st) {
+template <int D, int NQ, bool HIO>
+static int launch_fwd_bf16(AttnDev d, hipStream_t st, const char* who) {
   using C = CfgH<D>;
   static unsigned lds_set = 0;
   const int bytes = 2 * ((KV * C::SK + KV * C::SV + 7) / 8 * 8) * (int)sizeof(unsigned short);
-  if (set_lds(attn_fwd_bf16_kernel<D, NQ>, bytes, "gad_attention_fwd", &lds_set)) return 1;
+  if (set_lds(attn_fwd_bf16_kernel<D, NQ, HIO>, bytes, who, &lds_set)) return 1;
   const dim3 grid = grid_of(d, d.Tq, 64 * NQ);
-  hipLaunchKernelGGL((attn_fwd_bf16_kernel<D, NQ>), grid, dim3(NT), bytes, st, d);
+  hipLaunchKernelGGL((attn_fwd_bf16_kernel<D, NQ, HIO>), grid, dim3(NT), bytes, st, d);
   return 0;
 }
 
+static dim3 delta_grid(const AttnDev& d) { return dim3((unsigned)gad_ceil_div((long)d.B * d.Tq * d.heads, 256)); }
+
 template <int D, bool RG>
-static int launch_bwd(AttnDev d, float* delta, hipStream_t st) {
+static int launch_bwd(AttnDev d, float* delta, hipStream_t st, const char* who) {
   static unsigned lds_set_q = 0, lds_set_kv = 0;
   const int bytes = 4 * Cfg<D>::TILE * (int)sizeof(float);
-  constexpr int NQB = (D <= 80 && !RG) ? 2 : 1;      // query blocks per wave of the dQ kernel (registers allow two up to d = 80)
-  if (set_lds(attn_bwd_dq_f32_kernel<D, NQB, RG>, bytes, "gad_attention_bwd", &lds_set_q) ||
-      set_lds(attn_bwd_dkv_f32_kernel<D, RG>, bytes, "gad_attention_bwd", &lds_set_kv)) return 1;
-  const long total = (long)d.B * d.Tq * d.heads;
-  hipLaunchKernelGGL((attn_delta_kernel<D, RG>), dim3((unsigned)gad_ceil_div(total, 256)), dim3(256), 0, st, d, delta);
+  constexpr int NQB = pair_nqb(D, RG);
+  if (set_lds(attn_bwd_dq_f32_kernel<D, NQB, RG>, bytes, who, &lds_set_q) ||
+      set_lds(attn_bwd_dkv_f32_kernel<D, RG>, bytes, who, &lds_set_kv)) return 1;
+  hipLaunchKernelGGL((attn_delta_kernel<D, RG>), delta_grid(d), dim3(256), 0, st, d, delta);
   dim3 grid = grid_of(d, d.Tq, 64 * NQB);
   hipLaunchKernelGGL((attn_bwd_dq_f32_kernel<D, NQB, RG>), grid, dim3(NT), bytes, st, d);
   grid = grid_of(d, d.Tk, 64);
@@ -1663,42 +1767,15 @@ static int launch_bwd(AttnDev d, float* delta, hipStream_t st) {
   return 0;
 }
 
-// ---- single-pass backward: plan and launch ---------------------------------------------------------------------------
-// keys per workgroup = 64 NK; NK <= 4 up to d = 40, <= 2 up to 80, 1 at 96 (dK / dV accumulators + the K / V fragments of
-// NK key tiles per wave must fit the register file); among those the NK with the fewest padded keys, ties to the larger
-// (fewer dQ slabs: a single block writes dQ directly)
-static int bwd1_nk(int dinst, int Tk, long bh, int Tq) {
-  if (dinst > 96) return 0;
-  const int nkmax = dinst <= 40 ? 4 : dinst <= 80 ? 2 : 1;
-  int best = 0;
-  long best_pad = 0;
-  for (int nk = 1; nk <= nkmax; nk *= 2) {
-    const long nblk = gad_ceil_div(Tk, 64 * nk), pad = nblk * 64 * nk;
-    if (bh * nblk < 512 && nk > 1) continue;               // keep two workgroups per CU in flight
-    if (!best || pad <= best_pad) { best_pad = pad; best = nk; }
-  }
-  // few keys, many queries (cross attention over 77 text tokens at 64 x 64 latents): a key block per workgroup leaves
-  // most of the chip idle, the dQ kernel of the pair is parallel over the queries - keep the pair there
-  if (best == 1 && bh * gad_ceil_div(Tk, 64) < 512 && bh * gad_ceil_div(Tq, 128) > 4 * bh * gad_ceil_div(Tk, 64)) return 0;
-  return best;
-}
-static int64_t bwd1_ws_bytes(const gad_attention_args* a) {
-  const int nk = bwd1_nk(instance_dim(a->d), a->Tk, (long)a->B * a->heads, a->Tq);
-  if (!nk) return 0;
-  const long nblk = gad_ceil_div(a->Tk, 64 * nk);
-  return nblk > 1 ? nblk * (int64_t)a->B * a->Tq * a->heads * a->d * (int64_t)sizeof(float) : 0;
-}
-
 template <int D, int NK, bool RG>
-static int launch_bwd1(AttnDev d, float* delta, hipStream_t st) {
+static int launch_bwd1(AttnDev d, float* delta, hipStream_t st, const char* who) {
   using W = Bwd1<D, NK>;
   static unsigned lds_set = 0;
   const int bytes = W::LDS_FLOATS * (int)sizeof(float);
-  if (set_lds(attn_bwd1_f32_kernel<D, NK, RG>, bytes, "gad_attention_bwd", &lds_set)) return 1;
-  const long total = (long)d.B * d.Tq * d.heads;
-  hipLaunchKernelGGL((attn_delta_kernel<D, RG>), dim3((unsigned)gad_ceil_div(total, 256)), dim3(256), 0, st, d, delta);
+  if (set_lds(attn_bwd1_f32_kernel<D, NK, RG>, bytes, who, &lds_set)) return 1;
+  hipLaunchKernelGGL((attn_delta_kernel<D, RG>), delta_grid(d), dim3(256), 0, st, d, delta);
   const dim3 grid = grid_of(d, d.Tk, W::KB);
-  GAD_CHECK(d.nblk == 1 || d.ws, "gad_attention_bwd: %d key blocks but no dQ slab workspace", d.nblk);   // never a null store
+  GAD_CHECK(d.nblk == 1 || d.ws, "%s: %d key blocks but no dQ slab workspace", who, d.nblk);   // never a null store
   hipLaunchKernelGGL((attn_bwd1_f32_kernel<D, NK, RG>), grid, dim3(NT), bytes, st, d);
   if (d.nblk > 1) {
     const int wd = d.heads * d.d;
@@ -1709,34 +1786,8 @@ static int launch_bwd1(AttnDev d, float* delta, hipStream_t st) {
   }
   return 0;
 }
-template <int D, bool RG>
-static int bwd1_dim(const AttnDev& d, float* delta, hipStream_t st, int nk) {
-  if constexpr (D <= 96) {
-    if (nk == 1) return launch_bwd1<D, 1, RG>(d, delta, st);
-    if constexpr (D <= 80) { if (nk == 2) return launch_bwd1<D, 2, RG>(d, delta, st); }
-    if constexpr (D <= 40) { if (nk == 4) return launch_bwd1<D, 4, RG>(d, delta, st); }
-  }
-  gad_set_error("gad_attention_bwd: no single-pass instance for d = %d, NK = %d", D, nk);
-  return 1;
-}
 
-template <int D>
-static int launch_bwd_h(AttnDev d, float* delta, hipStream_t st) {
-  using C = CfgH<D>;
-  static unsigned lds_set_q = 0, lds_set_kv = 0;
-  const int bytes = (4 * KV * C::SV + 64) * (int)sizeof(unsigned short) + 4 * KV * (int)sizeof(float);     // (+ the dK/dV kernel's lse / delta rows)
-  if (set_lds(attn_bwd_dq_bf16_kernel<D>, bytes, "gad_attention_bwd", &lds_set_q) ||
-      set_lds(attn_bwd_dkv_bf16_kernel<D>, bytes, "gad_attention_bwd", &lds_set_kv)) return 1;
-  const long total = (long)d.B * d.Tq * d.heads;
-  hipLaunchKernelGGL((attn_delta_kernel<D>), dim3((unsigned)gad_ceil_div(total, 256)), dim3(256), 0, st, d, delta);
-  dim3 grid = grid_of(d, d.Tq, 64);
-  hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<D>), grid, dim3(NT), bytes, st, d);
-  grid = grid_of(d, d.Tk, 64);
-  hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<D>), grid, dim3(NT), bytes, st, d);
-  return 0;
-}
-
-// ---- half-precision I/O launchers (gad_h_attention_*): the bf16-operand kernels with 16-bit loads / stores ----
+// delta from bf16 o / d_o (the bf16-storage backward)
 template <int D>
 __global__ void attn_delta_h_kernel(const AttnDev p, float* delta) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1755,182 +1806,92 @@ __global__ void attn_delta_h_kernel(const AttnDev p, float* delta) {
   }
   delta[((long)b * p.heads + h) * p.Tq + q] = acc;
 }
-template <int D, int NQ>
-static int launch_fwd_hio(AttnDev d, hipStream_t st) {
-  using C = CfgH<D>;
-  static unsigned lds_set = 0;
-  const int bytes = 2 * ((KV * C::SK + KV * C::SV + 7) / 8 * 8) * (int)sizeof(unsigned short);
-  if (set_lds(attn_fwd_bf16_kernel<D, NQ, true>, bytes, "gad_h_attention_fwd", &lds_set)) return 1;
-  const dim3 grid = grid_of(d, d.Tq, 64 * NQ);
-  hipLaunchKernelGGL((attn_fwd_bf16_kernel<D, NQ, true>), grid, dim3(NT), bytes, st, d);
-  return 0;
-}
-template <int D>
-static int launch_bwd_hio(AttnDev d, float* delta, hipStream_t st) {
+
+template <int D, bool HIO>
+static int launch_bwd_bf16(const Route& r, AttnDev d, float* delta, hipStream_t st, const char* who) {
   using C = CfgH<D>;
   static unsigned lds_set_q = 0, lds_set_kv = 0;
   const int bytes = (4 * KV * C::SV + 64) * (int)sizeof(unsigned short) + 4 * KV * (int)sizeof(float);     // (+ the dK/dV kernel's lse / delta rows)
-  if (set_lds(attn_bwd_dq_bf16_kernel<D, true>, bytes, "gad_h_attention_bwd", &lds_set_q) ||
-      set_lds(attn_bwd_dkv_bf16_kernel<D, true>, bytes, "gad_h_attention_bwd", &lds_set_kv)) return 1;
-  const long total = (long)d.B * d.Tq * d.heads;
-  hipLaunchKernelGGL((attn_delta_h_kernel<D>), dim3((unsigned)gad_ceil_div(total, 256)), dim3(256), 0, st, d, delta);
-  // 32 rows per wave (128 per workgroup) while the grid still fills the chip twice over (head dims up to 96)
-  bool two_q = false, two_k = false;
-  if constexpr (D <= 96) {
-    two_q = gad_ceil_div(d.Tq, 128) * d.B * d.heads >= 512;
-    two_k = gad_ceil_div(d.Tk, 128) * d.B * d.heads >= 512;
+  if (set_lds(attn_bwd_dq_bf16_kernel<D, HIO>, bytes, who, &lds_set_q) ||
+      set_lds(attn_bwd_dkv_bf16_kernel<D, HIO>, bytes, who, &lds_set_kv)) return 1;
+  if constexpr (HIO) {
+    hipLaunchKernelGGL((attn_delta_h_kernel<D>), delta_grid(d), dim3(256), 0, st, d, delta);
+  } else {
+    hipLaunchKernelGGL((attn_delta_kernel<D>), delta_grid(d), dim3(256), 0, st, d, delta);
   }
-  if constexpr (D <= 96) {
-    if (two_q) {
-      const dim3 grid = grid_of(d, d.Tq, 128);
-      hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<D, true, 2>), grid, dim3(NT), bytes, st, d);
-    }
-  }
-  if (!two_q) {
-    const dim3 grid = grid_of(d, d.Tq, 64);
-    hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<D, true>), grid, dim3(NT), bytes, st, d);
-  }
-  if constexpr (D <= 96) {
-    if (two_k) {
-      const dim3 grid = grid_of(d, d.Tk, 128);
-      hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<D, true, 2>), grid, dim3(NT), bytes, st, d);
-    }
-  }
-  if (!two_k) {
-    const dim3 grid = grid_of(d, d.Tk, 64);
-    hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<D, true>), grid, dim3(NT), bytes, st, d);
-  }
-  return 0;
-}
-template <int D>
-static int fwd_dim_hio(const AttnDev& d, hipStream_t st, bool wide) {
-  // (64 queries per wave measured slower than 32 at d = 40, T = 4096: 731 vs 675 us)
-  if constexpr (D <= 96) { if (wide) return launch_fwd_hio<D, 2>(d, st); }
-  return launch_fwd_hio<D, 1>(d, st);
-}
-// bf16 I/O contract: head dim an exact instance (multiple of 8, <= 160), 16-byte aligned rows (strides multiples of 8 elements)
-static int check_hio(const gad_attention_args* a, bool bwd, const char* who) {
-  if (check_common(a, who)) return 1;
-  GAD_CHECK(exact_instance(a->d) && a->d <= 160, "%s: head dim %d has no bf16-I/O instance", who, a->d);
-  auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  GAD_CHECK(al(a->q) && al(a->k) && al(a->v) && al(a->o), "%s: q / k / v / o must be 16-byte aligned", who);
-  GAD_CHECK(a->ldq % 8 == 0 && a->ldk % 8 == 0 && a->ldv % 8 == 0 && a->ldo % 8 == 0 && a->stride_q % 8 == 0 && a->stride_k % 8 == 0 &&
-            a->stride_v % 8 == 0 && a->stride_o % 8 == 0, "%s: strides must be multiples of 8 elements", who);
-  if (bwd) {
-    GAD_CHECK(a->lse && a->d_o && a->delta && a->dq && a->dk && a->dv, "%s: null pointer (lse / d_o / delta / dq / dk / dv)", who);
-    GAD_CHECK(al(a->d_o) && al(a->dq) && al(a->dk) && al(a->dv), "%s: gradients must be 16-byte aligned", who);
-    GAD_CHECK(a->ld_do % 8 == 0 && a->ld_dq % 8 == 0 && a->ld_dk % 8 == 0 && a->ld_dv % 8 == 0 && a->stride_do % 8 == 0 &&
-              a->stride_dq % 8 == 0 && a->stride_dk % 8 == 0 && a->stride_dv % 8 == 0, "%s: gradient strides must be multiples of 8 elements", who);
-    const int w = a->heads * a->d;
-    GAD_CHECK(a->ld_do >= w && a->ld_dq >= w && a->ld_dk >= w && a->ld_dv >= w, "%s: a gradient row stride is smaller than heads*d = %d", who, w);
-  }
+  // NU = 2 (32 rows per wave, 128 per workgroup) exists for bf16 storage only
+  constexpr bool TWO = HIO && bf16_has_two(D);
+  const int nu_q = TWO ? r.nu_q : 1, nu_kv = TWO ? r.nu_kv : 1;
+  dim3 grid = grid_of(d, d.Tq, 64 * nu_q);
+  if constexpr (TWO) { if (nu_q == 2) hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<D, HIO, 2>), grid, dim3(NT), bytes, st, d); }
+  if (nu_q == 1) hipLaunchKernelGGL((attn_bwd_dq_bf16_kernel<D, HIO>), grid, dim3(NT), bytes, st, d);
+  grid = grid_of(d, d.Tk, 64 * nu_kv);
+  if constexpr (TWO) { if (nu_kv == 2) hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<D, HIO, 2>), grid, dim3(NT), bytes, st, d); }
+  if (nu_kv == 1) hipLaunchKernelGGL((attn_bwd_dkv_bf16_kernel<D, HIO>), grid, dim3(NT), bytes, st, d);
   return 0;
 }
 
-// one instance dim: pick the form (RG / bf16 / f32, queries per workgroup)
-template <int D>
-static int fwd_dim(const AttnDev& d, hipStream_t st, bool rg, bool bf16, bool wide, bool two_kernel_legacy) {
-  if (rg) return launch_fwd<D, 1, true>(d, st);
-  if (bf16) {
-    if constexpr (D <= 96) { if (wide) return launch_fwd_h<D, 2>(d, st); }
-    return launch_fwd_h<D, 1>(d, st);
-  }
-  if constexpr (D <= 80) { if (wide) return launch_fwd<D, 2, false>(d, st); }
-  if constexpr (D >= 160 && D % 32 == 0) { if (!two_kernel_legacy) return launch_fwd_wide<D>(d, st); }
-  return launch_fwd<D, 1, false>(d, st);
+// ---- dispatch: the route's form at one instance dim ----------------------------------------------------------------------
+template <int D, bool HIO>
+static int fwd_bf16(const Route& r, const AttnDev& d, hipStream_t st, const char* who) {
+  if constexpr (bf16_has_two(D)) { if (r.nq == 2) return launch_fwd_bf16<D, 2, HIO>(d, st, who); }
+  return launch_fwd_bf16<D, 1, HIO>(d, st, who);
+}
+template <int D, bool RG>
+static int bwd1(const Route& r, const AttnDev& d, float* delta, hipStream_t st, const char* who) {
+  if constexpr (bwd1_max_nk(D) >= 1) { if (r.nk == 1) return launch_bwd1<D, 1, RG>(d, delta, st, who); }
+  if constexpr (bwd1_max_nk(D) >= 2) { if (r.nk == 2) return launch_bwd1<D, 2, RG>(d, delta, st, who); }
+  if constexpr (bwd1_max_nk(D) >= 4) { if (r.nk == 4) return launch_bwd1<D, 4, RG>(d, delta, st, who); }
+  gad_set_error("%s: no single-pass instance for d = %d, NK = %d", who, D, r.nk);
+  return 1;
 }
 template <int D>
-static int bwd_dim(const AttnDev& d, float* delta, hipStream_t st, bool rg, bool bf16, int nk1) {
-  if (nk1) return rg ? bwd1_dim<D, true>(d, delta, st, nk1) : bwd1_dim<D, false>(d, delta, st, nk1);
-  if (rg) return launch_bwd<D, true>(d, delta, st);
-  if (bf16) return launch_bwd_h<D>(d, delta, st);
-  return launch_bwd<D, false>(d, delta, st);
+static int launch_dim(const Route& r, Pass pass, Io io, const AttnDev& d, float* delta, hipStream_t st, const char* who) {
+  if (io == IO_BF16) {
+    if constexpr (hio_instance(D)) return pass == FORWARD ? fwd_bf16<D, true>(r, d, st, who) : launch_bwd_bf16<D, true>(r, d, delta, st, who);
+    gad_set_error("%s: head dim %d has no bf16-I/O instance", who, D);
+    return 1;
+  }
+  if (pass == FORWARD) {
+    if (r.rg) return launch_fwd<D, 1, true>(d, st, who);
+    if (r.bf16) return fwd_bf16<D, false>(r, d, st, who);
+    if constexpr (fwd_f32_has_nq2(D)) { if (r.nq == 2) return launch_fwd<D, 2, false>(d, st, who); }
+    if constexpr (fwd_has_wide_head(D)) { if (r.wide_head) return launch_fwd_wide<D>(d, st, who); }
+    return launch_fwd<D, 1, false>(d, st, who);
+  }
+  if (r.nk) return r.rg ? bwd1<D, true>(r, d, delta, st, who) : bwd1<D, false>(r, d, delta, st, who);
+  if (r.rg) return launch_bwd<D, true>(d, delta, st, who);
+  if (r.bf16) return launch_bwd_bf16<D, false>(r, d, delta, st, who);
+  return launch_bwd<D, false>(d, delta, st, who);
+}
+
+static int launch(const gad_attention_args* a, Pass pass, Io io, void* stream, const char* who) {
+  if (check_args(a, pass, io, who)) return 1;
+  const Route r = route_of(a, pass, io);
+  const AttnDev d = make_dev(a);
+  int rc = 1;
+  switch (r.dim) {
+#define X(DIM) case DIM: rc = launch_dim<DIM>(r, pass, io, d, a->delta, (hipStream_t)stream, who); break;
+    GAD_ATTN_DIMS(X)
+#undef X
+  }
+  if (rc) return rc;
+  GAD_LAUNCH_CHECK(who);
+  return 0;
 }
 
 }  // namespace
 
+// the single-pass kernel's dQ slabs, if this launch takes that kernel when given them; else 0
 extern "C" int64_t gad_attention_bwd_workspace_bytes(const gad_attention_args* a) {
-  if (!a || !gad_attention_supported(a->d) || a->B <= 0 || a->heads <= 0 || a->Tq <= 0 || a->Tk <= 0) return 0;
-  if (a->operand_precision == 1 && fast_contract(a, true)) return 0;        // bf16 launches run the two-kernel pair
-  return bwd1_ws_bytes(a);
+  return a ? route_of(a, BACKWARD, IO_F32, WS_GRANTED).ws_bytes : 0;
 }
-
 // 1 if this launch runs bf16-operand kernels (operand_precision = 1 AND the float4 contract holds; RG launches are fp32)
 extern "C" int gad_attention_uses_bf16(const gad_attention_args* a, int32_t backward) {
-  return a && a->operand_precision == 1 && fast_contract(a, backward != 0);
+  return a && route_of(a, backward ? BACKWARD : FORWARD, IO_F32, WS_GRANTED).bf16;
 }
-
-extern "C" int gad_attention_fwd(const gad_attention_args* a, void* stream) {
-  if (check_common(a, "gad_attention_fwd")) return 1;
-  const AttnDev d = make_dev(a);
-  hipStream_t st = (hipStream_t)stream;
-  const bool rg = !fast_contract(a, false), bf16 = a->operand_precision == 1;
-  // queries per workgroup: 128 while the (b, h, block) grid still fills the chip twice over, else 64
-  const bool wide = gad_ceil_div(a->Tq, 128) * a->B * a->heads >= 512;
-  int rc = 1;
-  switch (instance_dim(a->d)) {
-#define X(DIM) case DIM: rc = fwd_dim<DIM>(d, st, rg, bf16, wide, (a->flags & GAD_ATTN_NARROW_FWD) != 0); break;
-    GAD_ATTN_DIMS(X)
-#undef X
-  }
-  if (rc) return rc;
-  GAD_LAUNCH_CHECK("gad_attention_fwd");
-  return 0;
-}
-
-extern "C" int gad_attention_bwd(const gad_attention_args* a, void* stream) {
-  if (check_common(a, "gad_attention_bwd")) return 1;
-  GAD_CHECK(a->lse && a->d_o && a->delta && a->dq && a->dk && a->dv, "gad_attention_bwd: null pointer (lse / d_o / delta / dq / dk / dv)");
-  const int w = a->heads * a->d;
-  GAD_CHECK(a->ld_do >= w && a->ld_dq >= w && a->ld_dk >= w && a->ld_dv >= w, "gad_attention_bwd: a gradient row stride is smaller than heads*d = %d", w);
-  const AttnDev d = make_dev(a);
-  hipStream_t st = (hipStream_t)stream;
-  const bool rg = !fast_contract(a, true), bf16 = a->operand_precision == 1;
-  // single-pass kernel: exact-fp32 launches up to d = 96 whose dQ slabs fit the caller's workspace (flags bit 0 keeps the
-  // dQ + dK/dV pair: A/B tools, tests); everything else - wider heads, bf16 operands - runs the pair
-  int nk1 = (bf16 && !rg) || (a->flags & GAD_ATTN_TWO_KERNEL_BWD) ? 0 : bwd1_nk(instance_dim(a->d), a->Tk, (long)a->B * a->heads, a->Tq);
-  if (nk1) {
-    const int64_t need = bwd1_ws_bytes(a);
-    if (need > 0 && !(a->ws && a->ws_bytes >= need && gad_aligned16(a->ws))) nk1 = 0;
-  }
-  int rc = 1;
-  switch (instance_dim(a->d)) {
-#define X(DIM) case DIM: rc = bwd_dim<DIM>(d, a->delta, st, rg, bf16, nk1); break;
-    GAD_ATTN_DIMS(X)
-#undef X
-  }
-  if (rc) return rc;
-  GAD_LAUNCH_CHECK("gad_attention_bwd");
-  return 0;
-}
-
-#define GAD_ATTN_HIO_DIMS(X) X(16) X(24) X(32) X(40) X(48) X(64) X(80) X(96) X(128) X(160)
-extern "C" int gad_h_attention_fwd(const gad_attention_args* a, void* stream) {
-  if (check_hio(a, false, "gad_h_attention_fwd")) return 1;
-  const AttnDev d = make_dev(a);
-  hipStream_t st = (hipStream_t)stream;
-  const bool wide = gad_ceil_div(a->Tq, 128) * a->B * a->heads >= 512;
-  int rc = 1;
-  switch (a->d) {
-#define X(DIM) case DIM: rc = fwd_dim_hio<DIM>(d, st, wide); break;
-    GAD_ATTN_HIO_DIMS(X)
-#undef X
-  }
-  if (rc) return rc;
-  GAD_LAUNCH_CHECK("gad_h_attention_fwd");
-  return 0;
-}
-extern "C" int gad_h_attention_bwd(const gad_attention_args* a, void* stream) {
-  if (check_hio(a, true, "gad_h_attention_bwd")) return 1;
-  const AttnDev d = make_dev(a);
-  hipStream_t st = (hipStream_t)stream;
-  int rc = 1;
-  switch (a->d) {
-#define X(DIM) case DIM: rc = launch_bwd_hio<DIM>(d, a->delta, st); break;
-    GAD_ATTN_HIO_DIMS(X)
-#undef X
-  }
-  if (rc) return rc;
-  GAD_LAUNCH_CHECK("gad_h_attention_bwd");
-  return 0;
-}
+extern "C" int gad_attention_fwd(const gad_attention_args* a, void* stream) { return launch(a, FORWARD, IO_F32, stream, "gad_attention_fwd"); }
+extern "C" int gad_attention_bwd(const gad_attention_args* a, void* stream) { return launch(a, BACKWARD, IO_F32, stream, "gad_attention_bwd"); }
+// bf16 q / k / v / o / d_o / dq / dk / dv (fp32 lse / delta): the bf16-operand kernels with 16-bit loads / stores
+extern "C" int gad_h_attention_fwd(const gad_attention_args* a, void* stream) { return launch(a, FORWARD, IO_BF16, stream, "gad_h_attention_fwd"); }
+extern "C" int gad_h_attention_bwd(const gad_attention_args* a, void* stream) { return launch(a, BACKWARD, IO_BF16, stream, "gad_h_attention_bwd"); }

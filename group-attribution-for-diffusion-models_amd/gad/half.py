@@ -13,12 +13,11 @@ Every FLOP runs in libgad_hip.so; there is no CPU fallback."""
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 
 from . import _capi, ops
-from ._capi import AttentionArgs, GroupNormArgs, HGemmArgs, check
+from ._capi import GroupNormArgs, HGemmArgs, check
 
 BF16 = torch.bfloat16
 
@@ -664,15 +663,8 @@ class HGegluFn(torch.autograd.Function):
 
 
 def _attn_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, scale):
-    a = AttentionArgs()
-    a.q, a.k, a.v, a.o, a.lse = q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), (lse.data_ptr() if lse is not None else None)
-    a.B, a.heads, a.Tq, a.Tk, a.d = Bn, heads, Tq, Tk, d
     Cq = heads * d
-    a.ldq = a.ldk = a.ldv = a.ldo = Cq
-    a.stride_q, a.stride_k, a.stride_v, a.stride_o = Tq * Cq, Tk * Cq, Tk * Cq, Tq * Cq
-    a.scale = 1.0 / math.sqrt(d) if scale is None else scale
-    if scale is not None:
-        a.alg_d = int(round(1.0 / (scale * scale)))
+    a = ops._attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, Cq, Cq, Cq, Tq * Cq, Tk * Cq, Tk * Cq, scale)
     a.operand_precision = 1
     return a
 
@@ -708,11 +700,8 @@ class HAttentionFn(torch.autograd.Function):
         dq, dk, dv = _empty(q.shape, q.device), _empty(k.shape, k.device), _empty(v.shape, v.device)
         delta = _empty(lse.shape, lse.device, torch.float32)
         a = _attn_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, ctx.scale)
-        a.d_o, a.delta, a.dq, a.dk, a.dv = do.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-        a.ld_do = a.ld_dq = a.ld_dk = a.ld_dv = Cq
-        a.stride_do = a.stride_dq = Tq * Cq
-        a.stride_dk = a.stride_dv = Tk * Cq
-        fn = _capi.load().gad_h_attention_bwd
+        ops._attention_grad_args(a, do, delta, dq, dk, dv, Cq, Tq * Cq, Tk * Cq)
+        fn =_capi.load().gad_h_attention_bwd
         if ops.PROFILER is not None:
             ops.PROFILER.attention(fn, a, "bwd", elem_bytes=2)
         else:

@@ -1306,6 +1306,15 @@ def _attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, sq, sk
     return a
 
 
+def _attention_grad_args(a, do, delta, dq, dk, dv, ld, sq, sk):
+    """The backward's fields of `a`: gradient pointers, their row stride, batch strides of the query / key side."""
+    a.d_o, a.delta, a.dq, a.dk, a.dv = do.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
+    a.ld_do = a.ld_dq = a.ld_dk = a.ld_dv = ld
+    a.stride_do = a.stride_dq = sq
+    a.stride_dk = a.stride_dv = sk
+    return a
+
+
 def attention_fwd_raw(q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse=True, scale=None):
     """Fused attention forward on [Bn, T, *] views (q, k, v may be column blocks of one projection output: their
     data_ptr is the column offset, ld* the row stride).  -> (o [Bn, Tq, heads*d], lse [Bn, heads, Tq] or None)"""
@@ -1350,11 +1359,8 @@ class AttentionCoreFn(torch.autograd.Function):
         dq, dk, dv = _out(q.shape, q.device), _out(k.shape, k.device), _out(v.shape, v.device)
         delta = _out(lse.shape, lse.device)
         a = _attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, Cq, Cq, Cq, Tq * Cq, Tk * Cq, Tk * Cq, ctx.scale)
-        a.d_o, a.delta, a.dq, a.dk, a.dv = do.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-        a.ld_do = a.ld_dq = a.ld_dk = a.ld_dv = Cq
-        a.stride_do = a.stride_dq = Tq * Cq
-        a.stride_dk = a.stride_dv = Tk * Cq
-        a.operand_precision = ctx.prec                   # the precision the forward's LSE was computed in
+        _attention_grad_args(a, do, delta, dq, dk, dv, Cq, Tq * Cq, Tk * Cq)
+        a.operand_precision = ctx.prec                  # the precision the forward's LSE was computed in
         a.flags = _capi.ATTN_TWO_KERNEL_BWD if KERNEL_FLAGS.get("two_kernel_attn_bwd") else 0
         need = _capi.load().gad_attention_bwd_workspace_bytes(C.byref(a))
         if need:                                         # dQ partial slabs of the single-pass kernel (one per key block)

@@ -273,6 +273,10 @@ typedef struct gad_attention_args {
 } gad_attention_args;
 #define GAD_ATTN_TWO_KERNEL_BWD 1   /* bwd: keep the recomputing dQ + dK/dV kernel pair (A/B tools, tests) */
 #define GAD_ATTN_NARROW_FWD 2       /* fwd: keep the 4-wave kernel for d >= 160 instead of the 8-wave split-head-dim kernel (A/B) */
+/* Bytes of `ws` the backward launch of these arguments uses if it is given them: the single-pass kernel's dQ slabs (key
+ * blocks x B x Tq x heads x d floats; one key block writes dQ directly), 0 for every launch that runs the dQ + dK/dV pair -
+ * d > 96, bf16 operands, few keys under many queries, GAD_ATTN_TWO_KERNEL_BWD - and for arguments gad_attention_bwd refuses.
+ * Reads shapes, strides, flags and pointer alignment only (not ws / ws_bytes); the same route decision as the launch. */
 int64_t gad_attention_bwd_workspace_bytes(const gad_attention_args* a);
 int gad_attention_supported(int32_t d);      /* 1 if 1 <= d <= 256 */
 int gad_attention_uses_bf16(const gad_attention_args* a, int32_t backward);   /* 1 if this launch multiplies bf16 operands */

@@ -370,3 +370,77 @@ def test_winograd_stage_flags_are_refused_off_their_route():
     wg = _route_args(_capi.A_MC, _capi.B_CONV, 128, 9 * 128, 128 * 32 * 32, (32, 32, 128, 32, 32, 3, 1, 1, 0))
     wg.flags = _capi.GEMM_WINO_WGRAD | _capi.GEMM_WINO_ONLY_INPUT
     assert kid(wg) == 7 and refused(wg, "GAD_GEMM_WINO_ONLY_INPUT")
+
+
+# ---- the attention router's table: its three host queries over a fixed grid, against tests/golden/attention_routes.npz ----
+ATTN_ROUTE_COLUMNS = ("ws_bytes", "uses_bf16_fwd", "uses_bf16_bwd")
+ATTN_DIMS = (1, 8, 16, 23, 24, 32, 40, 41, 48, 64, 80, 88, 96, 97, 128, 160, 192, 224, 256, 257)
+ATTN_BH = ((1, 1), (1, 8), (2, 8), (2, 21), (4, 16), (16, 8), (64, 1), (64, 8), (128, 5), (256, 2), (1024, 1))
+ATTN_T = ((4096, 4096), (4096, 77), (256, 77), (100, 300), (64, 4096), (16, 16), (1024, 1024), (520, 260))
+
+
+def attention_route_grid():
+    """The grid the attention route table is recorded on, as (gad_attention_args, case tuple): head dims on and off the
+    instances (257: unsupported), (B, heads) from 1 to 1024 blocks, self- and cross-attention lengths, row strides on and off
+    the float4 contract, q 16-byte aligned or not, both operand precisions, no flag / two-kernel backward / narrow forward."""
+    for d in ATTN_DIMS:
+        for B, heads in ATTN_BH:
+            for Tq, Tk in ATTN_T:
+                for pad in (0, 2, 4):
+                    for mis in (0, 4):
+                        for prec in (0, 1):
+                            for flags in (0, 1, 2):
+                                a, ld = _capi.AttentionArgs(), heads * d + pad
+                                a.q, a.k, a.v, a.o, a.lse = _P + mis, 2 * _P, 3 * _P, 4 * _P, 5 * _P
+                                a.d_o, a.delta, a.dq, a.dk, a.dv = 6 * _P, 7 * _P, 8 * _P, 9 * _P, 10 * _P
+                                a.B, a.heads, a.Tq, a.Tk, a.d = B, heads, Tq, Tk, d
+                                a.ldq = a.ldk = a.ldv = a.ldo = a.ld_do = a.ld_dq = a.ld_dk = a.ld_dv = ld
+                                a.stride_q = a.stride_o = a.stride_do = a.stride_dq = Tq * ld
+                                a.stride_k = a.stride_v = a.stride_dk = a.stride_dv = Tk * ld
+                                a.scale, a.operand_precision, a.flags = d ** -0.5, prec, flags
+                                yield a, (d, B, heads, Tq, Tk, pad, mis, prec, flags)
+
+
+def attention_route_table(lib):
+    """The three queries of every grid case as int64 columns (ATTN_ROUTE_COLUMNS), and the cases as an int64 matrix."""
+    import numpy as np
+    rows, cases = [], []
+    for a, case in attention_route_grid():
+        r = ctypes.byref(a)
+        rows.append((lib.gad_attention_bwd_workspace_bytes(r), lib.gad_attention_uses_bf16(r, 0), lib.gad_attention_uses_bf16(r, 1)))
+        cases.append(case)
+    return dict(zip(ATTN_ROUTE_COLUMNS, np.array(rows, dtype=np.int64).T)), np.array(cases, dtype=np.int64)
+
+
+def test_attention_route_table_matches_the_recorded_one(golden_dir):
+    """Both attention queries read the one Route route_of resolves (csrc/attention.hip): the workspace bytes and the two bf16
+    answers over the grid are the ones recorded from the library before that refactor (tests/golden/attention_routes.npz).
+    The one deliberate change: with GAD_ATTN_TWO_KERNEL_BWD the launch runs the dQ + dK/dV pair and uses no workspace, and
+    the size query now says so - 0 bytes, where the old one answered with the single-pass kernel's slabs."""
+    import numpy as np
+    want = dict(np.load(os.path.join(golden_dir, "attention_routes.npz")))
+    got, cases = attention_route_table(_capi.load())
+    d, B, heads, Tq, Tk, pad, mis, prec, flags = cases.T
+    assert len(got["ws_bytes"]) == len(want["ws_bytes"]) == len(ATTN_DIMS) * len(ATTN_BH) * len(ATTN_T) * 3 * 2 * 2 * 3
+    pair = (flags & _capi.ATTN_TWO_KERNEL_BWD) != 0
+    assert (want["ws_bytes"][pair] > 0).any()
+    want["ws_bytes"][pair] = 0
+    for c in ATTN_ROUTE_COLUMNS:
+        bad = np.nonzero(got[c] != want[c])[0]
+        assert len(bad) == 0, f"{c}: {len(bad)} cases differ, first {cases[bad[:5]].tolist()}: {got[c][bad[:5]].tolist()} != {want[c][bad[:5]].tolist()}"
+    # what the grid covers
+    ws, bf_f, bf_b = (got[c] for c in ATTN_ROUTE_COLUMNS)
+    slab = B * Tq * heads * d * 4
+    assert (ws % slab == 0).all()
+    blocks = ws // slab                                            # key blocks of the single-pass launches that take slabs
+    assert (blocks == 2).any() and (blocks == 4).any() and (blocks > 4).any() and not (blocks == 1).any()
+    fp32 = ~pair & (prec == 0)
+    assert (ws[d > 96] == 0).all() and (fp32 & (d > 96) & (d <= 256)).any()                 # no single-pass instance
+    few = fp32 & (d <= 96) & (B * heads == 1) & (Tk == 77)                                  # the few-keys rule keeps the pair
+    assert (ws[few & (Tq == 4096)] == 0).all() and (ws[few & (Tq == 256)] > 0).all() and (few & (Tq == 4096)).any()
+    assert (bf_f == 1).any() and (bf_b == 1).any() and (ws[bf_b == 1] == 0).all()           # bf16 launches run the pair
+    rg = (pad == 2) | (mis != 0) | ~np.isin(d, (16, 24, 32, 40, 48, 64, 80, 96, 128, 160, 192, 224, 256))
+    assert (bf_f[rg] == 0).all() and (bf_b[rg] == 0).all() and (rg & (prec == 1)).any()     # RG launches answer fp32
+    assert (bf_b[~rg & (prec == 1)] == 1).all() and (bf_b[prec == 0] == 0).all()
+    assert (rg & (prec == 1) & (ws > 0)).any()                                              # ... and take the single-pass kernel
+    assert (d == 257).any() and (ws[d == 257] == 0).all() and (bf_f[d == 257] == 0).all()  # unsupported head dim

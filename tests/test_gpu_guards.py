@@ -114,9 +114,7 @@ def test_attention_backward_without_workspace_falls_back(ops):
         for give in ("exact", "none", "short"):
             dq, dk, dv, delta = torch.zeros_like(q), torch.zeros_like(k), torch.zeros_like(v), torch.empty_like(lse)
             a = ops._attention_args(q, k, v, o, lse, B, heads, T, T, d, C, C, C, T * C, T * C, T * C)
-            a.d_o, a.delta, a.dq, a.dk, a.dv = do.data_ptr(), delta.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr()
-            a.ld_do = a.ld_dq = a.ld_dk = a.ld_dv = C
-            a.stride_do = a.stride_dq = a.stride_dk = a.stride_dv = T * C
+            ops._attention_grad_args(a, do, delta, dq, dk, dv, C, T * C, T * C)
             a.operand_precision = prec
             need = lib.gad_attention_bwd_workspace_bytes(_capi.C.byref(a))
             assert need == 4 * B * T * C * 4          # 4 key blocks of 64: the d = 23 launch takes the single-pass kernel in either mode
