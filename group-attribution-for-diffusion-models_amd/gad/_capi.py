@@ -112,7 +112,7 @@ GEMM_WINO_ONLY_INPUT, GEMM_WINO_SKIP_INPUT = 64, 128
 A_KC, A_MC, A_CONV, A_CONVT = 0, 1, 2, 3
 B_KC, B_MC, B_WDGRAD, B_CONV = 0, 1, 2, 3
 
-_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_vp, _i32, _i64, _f32, _f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol include/gad.h declares
 SIGNATURES = {
@@ -187,6 +187,12 @@ SIGNATURES = {
     # random projection (csrc/projector.hip)
     "gad_jl_project_workspace_bytes": (_i64, [C.POINTER(JLArgs)]),
     "gad_jl_project": (C.c_int, [C.POINTER(JLArgs), _vp]),
+    # local model behaviours (csrc/local.hip)
+    "gad_image_metrics_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "gad_image_metrics": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _vp, _i64, _vp]),
+    "gad_add_noise_bcast": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "gad_mse_segments_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "gad_mse_segments": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
 }
 
 _lib = None

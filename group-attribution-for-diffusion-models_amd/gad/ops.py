@@ -1543,6 +1543,67 @@ def mse_fwd_bwd_raw(pred, target, grad_scale=1.0):
     return loss, d
 
 
+# ---- local model behaviours (csrc/local.hip) ----
+def image_metrics_raw(a, b, win=7, data_range=1.0, K1=0.01, K2=0.03):
+    """a, b: [N][H][W][C] fp32 images -> [N][3] fp64 (mse, nrmse with `a` as image_true, ssim), scikit-image's definitions."""
+    _req(a, "image_metrics a")
+    _req(b, "image_metrics b")
+    if a.ndim != 4 or a.shape != b.shape:
+        raise _capi.GadError(f"image_metrics: expected two [N][H][W][C] tensors of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    N, H, W, Cc = a.shape
+    lib = _capi.load()
+    need = lib.gad_image_metrics_workspace_bytes(N, H, W, Cc, win)
+    if need < 0:
+        raise _capi.GadError(f"gad_image_metrics: {lib.gad_last_error().decode()}")
+    ws = _scratch("metrics_ws", need, a.device)
+    out = torch.empty((N, 3), device=a.device, dtype=torch.float64) if OUT_ALLOC_DT is None \
+        else OUT_ALLOC_DT((N, 3), a.device, torch.float64)
+    check(lib.gad_image_metrics(a.data_ptr(), b.data_ptr(), out.data_ptr(), N, H, W, Cc, win, data_range, K1, K2,
+                                ws.data_ptr(), need, _stream()), "gad_image_metrics")
+    return out
+
+
+def add_noise_bcast_raw(x0, eps, t, alphas_cumprod, rows_per_image, out=None):
+    """x0 [I][C][H][W], eps [R][C][H][W] (NCHW), t [T] int64 -> xt [R][H][W][C] (NHWC); row r: image r // rows_per_image,
+    timestep t[r % T]."""
+    _req(x0, "add_noise_bcast x0")
+    _req(eps, "add_noise_bcast eps")
+    _req(alphas_cumprod, "add_noise_bcast alphas_cumprod")
+    if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.ndim == 1):
+        raise _capi.GadError("add_noise_bcast t: expected a contiguous 1-D int64 device tensor")
+    R, Cc, H, W = eps.shape
+    if x0.ndim != 4 or tuple(x0.shape[1:]) != (Cc, H, W) or x0.shape[0] * rows_per_image != R:
+        raise _capi.GadError(f"add_noise_bcast: x0 {tuple(x0.shape)} does not hold one image per {rows_per_image} rows of eps {tuple(eps.shape)}")
+    out = _out((R, H, W, Cc), eps.device) if out is None else _req(out, "add_noise_bcast out")
+    if out.numel() != eps.numel():
+        raise _capi.GadError("add_noise_bcast: out does not have the size of eps")
+    check(_capi.load().gad_add_noise_bcast(x0.data_ptr(), eps.data_ptr(), t.data_ptr(), alphas_cumprod.data_ptr(), out.data_ptr(),
+                                           R, rows_per_image, t.shape[0], Cc, H * W, alphas_cumprod.numel(), _stream()),
+          "gad_add_noise_bcast")
+    return out
+
+
+def mse_segments_raw(pred, eps, rows_per_segment, out=None):
+    """pred [R][H][W][C] (NHWC), eps [R][C][H][W] (NCHW) -> [R // rows_per_segment] fp32 means of (pred - eps)^2."""
+    _req(pred, "mse_segments pred")
+    _req(eps, "mse_segments eps")
+    R, Cc, H, W = eps.shape
+    if tuple(pred.shape) != (R, H, W, Cc):
+        raise _capi.GadError(f"mse_segments: pred {tuple(pred.shape)} is not the NHWC shape of eps {tuple(eps.shape)}")
+    lib = _capi.load()
+    need = lib.gad_mse_segments_workspace_bytes(R, rows_per_segment, Cc, H * W)
+    if need < 0:
+        raise _capi.GadError(f"gad_mse_segments: {lib.gad_last_error().decode()}")
+    ws = _scratch("segments_ws", need, pred.device)
+    S = R // max(rows_per_segment, 1)
+    out = _out((S,), pred.device) if out is None else _req(out, "mse_segments out")
+    if out.numel() != S:
+        raise _capi.GadError(f"mse_segments: out holds {out.numel()} values for {S} segments")
+    check(lib.gad_mse_segments(pred.data_ptr(), eps.data_ptr(), out.data_ptr(), R, rows_per_segment, Cc, H * W, ws.data_ptr(), need,
+                               _stream()), "gad_mse_segments")
+    return out
+
+
 def sumsq_raw(g, out=None):
     ws = workspace(g.device)
     out = torch.empty(1, device=g.device, dtype=torch.float32) if out is None else out

@@ -1,5 +1,6 @@
 """Pipeline helpers with the reference's names and call signatures (src/diffusion_utils.py):
-load_ckpt_model :111-205, build_pipeline :208-316, generate_images :319-357, run_inference :360-416.
+load_ckpt_model :111-205, build_pipeline :208-316, generate_images :319-357, run_inference :360-416;
+local_behavior_row is the part the two local-behaviour entry points share (unlearn.py:859-958).
 `backend` is the module that supplies the diffusers-named classes: the MI355X engine `gad` by default."""
 import os
 
@@ -118,6 +119,29 @@ def generate_images(args, pipeline, fuse=32):
             q = x.mul(255).add_(0.5).clamp_(0, 255).to(torch.uint8)
             out.append(q.float().div_(255))
     return torch.cat(out, 0).float()
+
+
+def local_behavior_row(args, full_pipeline, pipeline, sample_outdir, backend=None):
+    """The local-behaviour keys of one jsonl row (unlearn.py:871-958, calculate_local_scores.py:303-384):
+    `generated_image_{s}_{mse,nrmse,ssim,diffusion_loss}` for seed s = 0..n_samples-1 and `avg_mse`, `avg_nrmse`, `avg_ssim`,
+    `avg_total_loss`, every value the string f"{v:.8e}" as the reference writes it; the full model's image of seed s is saved as
+    `{sample_outdir}/generated_image_{s}.png` (:916-919).  The numbers are `backend.local_model_behaviors`'s."""
+    from src.utils import save_image_grid
+    be = _backend(backend)
+    res = be.local_model_behaviors(full_pipeline, pipeline, args.n_samples, args.n_noises, args.num_inference_steps,
+                                   return_images=True)
+    full = torch.as_tensor(res["full_images"]).detach().cpu().float().permute(0, 3, 1, 2)
+    row = {}
+    for s in range(args.n_samples):
+        save_image_grid(full[s:s + 1], os.path.join(sample_outdir, f"generated_image_{s}.png"), padding=0)
+        for k in ("mse", "nrmse", "ssim", "diffusion_loss"):
+            row[f"generated_image_{s}_{k}"] = f"{res[k][s]:.8e}"
+    for k, name in (("mse", "avg_mse"), ("nrmse", "avg_nrmse"), ("ssim", "avg_ssim"), ("diffusion_loss", "avg_total_loss")):
+        row[name] = f"{sum(res[k]) / args.n_samples:.8e}"
+    space = getattr(res, "x0_space", "image")
+    if space != "image":          # CelebA: which tensor the diffusion loss saw (the VQ-VAE latent, or - without VQ-VAE weights -
+        row["diffusion_loss_input"] = space                     # the latent the pipeline hands out as its "image")
+    return row
 
 
 def _fused_sampler_for(pipeline, batch_size, fuse):

@@ -1,5 +1,6 @@
 """Sparsified fine-tuning ("unlearning") of a pre-trained DDPM on one contributor coalition, then the
-model-behaviour score and one jsonl row.
+model-behaviour score - global (FID / IS / precision / recall, `--model_behavior global`) or local (per generated image
+MSE / NRMSE / SSIM against the full model's image and the diffusion loss, `--model_behavior local`) - and one jsonl row.
 
 Entry point kept from the reference (unconditional_generation/unlearn.py): same flags for the sFT path
 (`--method gd`), same coalition semantics (the by_class quirk of :331 included), same jsonl keys
@@ -22,7 +23,8 @@ if _HERE not in sys.path:
 import src.constants as constants  # noqa: E402
 from src.datasets import (create_dataset, remove_data_by_datamodel, remove_data_by_loo,  # noqa: E402
                           remove_data_by_shapley, remove_data_by_uniform, remove_data_for_aoi)
-from src.diffusion_utils import build_pipeline, dataset_config, generate_images, load_ckpt_model  # noqa: E402
+from src.diffusion_utils import (build_pipeline, dataset_config, generate_images, load_ckpt_model,  # noqa: E402
+                                 local_behavior_row)
 from src.utils import save_image_grid  # noqa: E402
 
 
@@ -91,8 +93,6 @@ def main(args, backend=None):
     if args.method not in ("gd", "gd_u", "ga", "ga_u"):
         raise NotImplementedError(f"method={args.method}: the engine implements the sFT family (gd/ga); "
                                   "iu / lora / esd are baseline methods outside the hot path")
-    if args.model_behavior == "local":
-        raise NotImplementedError("local model behaviours (SSIM / per-image losses) are outside the hot path")
     if hasattr(backend, "set_operand_precision"):      # --mixed_precision fp16|bf16 -> bf16 operands, fp32 everything else
         backend.set_operand_precision(args.mixed_precision)
     device = torch.device(args.device)
@@ -156,6 +156,23 @@ def main(args, backend=None):
         else:
             info["fid_value"] = backend.fid_against_dataset(images, dataset, device, args.batch_size)
         print("; ".join(f"{k}: {info[k]}" for k in ("fid_value", "precision", "recall", "is") if k in info))
+    elif args.model_behavior == "local":                           # :839-958
+        full_model_dir = os.path.join(args.outdir, args.dataset, "retrain", "models", "full")
+        print(f"Loading full model checkpoint from {full_model_dir}")
+        method, trained_steps = args.method, args.trained_steps
+        args.method, args.trained_steps = "retrain", None
+        try:
+            full_model, full_ema_model, _, _ = load_ckpt_model(args, full_model_dir, backend)
+        finally:
+            args.method, args.trained_steps = method, trained_steps
+        full_model.to(device)
+        if args.use_ema:
+            full_ema_model.to(device)
+            full_ema_model.copy_to(full_model.parameters())
+        full_model.eval()
+        full_pipeline, _, _ = build_pipeline(args, full_model, backend)
+        info.update(local_behavior_row(args, full_pipeline, pipeline, sample_outdir, backend))
+        print("; ".join(f"{k}: {info[k]}" for k in ("avg_mse", "avg_nrmse", "avg_ssim", "avg_total_loss")))
     info.update(total_steps_time=total_steps_time, trained_steps=steps_goal,
                 remaining_idx=np.asarray(remaining_idx).tolist(), removed_idx=np.asarray(removed_idx).tolist(),
                 device=str(device), total_sampling_time=time.time() - t1)

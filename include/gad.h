@@ -535,6 +535,37 @@ typedef struct gad_jl_args {
 int64_t gad_jl_project_workspace_bytes(const gad_jl_args* a);
 int gad_jl_project(const gad_jl_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Local model behaviours of the unconditional models (csrc/local.hip; reference
+ * unconditional_generation/unlearn.py:871-948, calculate_local_scores.py:303-374).
+ * All three are order-deterministic (no atomics): a result depends on its own image / segment and on the
+ * geometry only, not on the batch size or the position in the batch.
+ *
+ * gad_image_metrics: N image pairs -> out[N][3] = (mse, nrmse, ssim) as fp64, with scikit-image's definitions for
+ *   mean_squared_error(a, b), normalized_root_mse(image_true = a, image_test = b) (euclidean normalisation) and
+ *   structural_similarity(a, b, channel_axis = -1, data_range): uniform win x win window, sample covariance, the map
+ *   cropped by (win - 1) / 2 on every side, mean over pixels and channels.  a, b: [N][H][W][C] fp32; win odd, 3..11;
+ *   H, W >= win.  Pixels are converted to fp64 before any product or difference; sums, the SSIM map and the means are fp64.
+ *   out and workspace 8-B aligned, workspace_bytes >= gad_image_metrics_workspace_bytes(...) (-1: arguments refused).
+ * gad_add_noise_bcast: row r of R belongs to image r / rows_per_image and timestep t[r % T]:
+ *   xt[r] = sqrt(ac[t]) x0[image] + sqrt(1 - ac[t]) eps[r];  x0 [R / rows_per_image][C][HW] and eps [R][C][HW] are NCHW,
+ *   xt [R][HW][C] is NHWC (the U-Net's input layout).  T divides rows_per_image, rows_per_image divides R;
+ *   alphas_cumprod has num_train_timesteps entries (a t outside the table yields NaN rows, no read).
+ * gad_mse_segments: out[s] = mean over rows s * rows_per_segment .. of (pred - eps)^2, pred [R][HW][C] NHWC, eps [R][C][HW]
+ *   NCHW; fp64 row sums, one fixed-order sum per segment, one rounding to fp32.  workspace 8-B aligned,
+ *   workspace_bytes >= gad_mse_segments_workspace_bytes(...).
+ * ---------------------------------------------------------------------------- */
+int64_t gad_image_metrics_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t C, int32_t win);
+int gad_image_metrics(const float* a, const float* b, double* out, int32_t N, int32_t H, int32_t W, int32_t C,
+                      int32_t win, double data_range, double K1, double K2, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+int gad_add_noise_bcast(const float* x0, const float* eps, const int64_t* t, const float* alphas_cumprod, float* xt,
+                        int32_t R, int32_t rows_per_image, int32_t T, int32_t C, int32_t HW, int32_t num_train_timesteps,
+                        void* stream);
+int64_t gad_mse_segments_workspace_bytes(int32_t R, int32_t rows_per_segment, int32_t C, int32_t HW);
+int gad_mse_segments(const float* pred, const float* eps, float* out, int32_t R, int32_t rows_per_segment, int32_t C,
+                     int32_t HW, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
