@@ -43,3 +43,9 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// GroupNorm forward (norm.hip, half.hip): sum x^2 - (sum x)^2 / n cancels where a group's mean lies far from zero against its
+// spread, and the result shows it: SS / m2 = 1 + (mean / std)^2 is the factor by which the sums' rounding is magnified.  Up to
+// GN_COND (|mean| / std < 3.9: four bits, inside what another summation order costs) the one-sweep sums stand; beyond it the
+// chunk is summed again, centred.
+constexpr float GN_COND = 16.f;

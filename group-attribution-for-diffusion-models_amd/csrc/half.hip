@@ -864,11 +864,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const u16* __restrict__ x, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// GroupNorm (+ SiLU), NHWC bf16.  Two launches: per-(image, row chunk, group) partial sums | apply, whose prologue reduces the
+// GroupNorm (+ SiLU), NHWC bf16.  Two launches: per-(image, row chunk, group) partials | apply, whose prologue reduces the
 // chunks' partials to the image's statistics in LDS (every workgroup of an image does the same few KB of L2 reads: cheaper than a
 // third launch).  A thread owns ONE channel octet (blockDim = NO * RP with NO = C / 8 octets, RP row phases), so its per-channel
 // coefficients are loop invariants and every access is a 16-B vector.
-//   forward  partials: (sum x, sum x^2)            statistics: mean, rstd
+//   forward  partials: (sum x, sum x^2), or (chunk mean, -centred m2) where those cancel (GN_COND)    statistics: mean, rstd
 //   backward partials: (sum g, sum g xhat), g = dy silu'(pre) gamma     statistics: s1 / n, s2 / n   (dx = rstd (g - s1/n - xhat s2/n))
 // ---------------------------------------------------------------------------------------------------------------
 struct GnDev {
@@ -887,9 +887,35 @@ __device__ __forceinline__ void gn_load(const GnDev& p, long pix, int o, float (
 __device__ __forceinline__ float silu_f(float v) { return v / (1.f + __expf(-v)); }
 __device__ __forceinline__ float silu_df(float v) { const float s = 1.f / (1.f + __expf(-v)); return s * (1.f + v * (1.f - s)); }
 
+// sum of a[8] (one per channel of the thread's octet) over the row phases, in a fixed order: channel c's sum in red[c]
+__device__ __forceinline__ void gn_octet_sum(float* red, float (&a)[8], const GnDev& p, int rp, int o) {
+  float* mine = red + ((long)rp * p.NO + o) * 8;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) mine[k] = a[k];
+  __syncthreads();
+  if (rp == 0) {
+    for (int q = 1; q < p.RP; ++q) {
+      const float* other = red + ((long)q * p.NO + o) * 8;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) a[k] += other[k];
+    }
+  }
+  __syncthreads();                       // every row phase's partials are read: the array is reused as [C] channel sums
+  if (rp == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) red[o * 8 + k] = a[k];
+  }
+  __syncthreads();
+}
+// Forward partials.  Where the one-sweep sums cancel (GN_COND, gad_common.h) the workgroup sweeps its chunk again for
+// (chunk mean, centred m2), which gn_apply_kernel merges with Chan's formula (tests/test_gpu_norm_conditioning.py,
+// profiles/gn_conditioning.txt).
 template <bool BWD>
 __global__ void gn_part_kernel(const GnDev p) {
-  extern __shared__ float red[];          // [RP][NO][16]
+  extern __shared__ float red[];          // [RP][NO][16]; forward: then [G] chunk means and the flag of a second sweep
+  float* smean = red + (long)p.RP * p.NO * 16;
+  int* ill = reinterpret_cast<int*>(smean + p.G);
+  if (!BWD && threadIdx.x == 0) *ill = 0;         // (the barriers ahead of the group loop order it)
   const int b = blockIdx.y, chunk = blockIdx.x;
   const int o = threadIdx.x % p.NO, rp = threadIdx.x / p.NO;
   const int cpg = p.C / p.G;
@@ -903,6 +929,7 @@ __global__ void gn_part_kernel(const GnDev p) {
     }
   }
   const int r0 = chunk * p.rows_per_chunk, r1 = min(p.HW, r0 + p.rows_per_chunk);
+  const float nrm = (float)(r1 - r0) * cpg;
   for (int r = r0 + rp; r < r1; r += p.RP) {
     const long pix = (long)b * p.HW + r;
     float f[8];
@@ -947,6 +974,31 @@ __global__ void gn_part_kernel(const GnDev p) {
     float* dst = p.part + (((long)b * p.chunks + chunk) * p.G + g) * 2;
     dst[0] = s0;
     dst[1] = s1;
+    if (!BWD) {
+      const float mean = s0 / nrm, m2 = s1 - s0 * mean;
+      smean[g] = mean;
+      if (!(s1 <= GN_COND * m2)) *ill = 1;       // the subtraction lost more than log2(GN_COND) bits: centred sums for this chunk
+    }
+  }
+  if (BWD) return;
+  __syncthreads();
+  if (!*ill) return;                             // (block-uniform)
+  // second sweep (the chunk comes from L2): sum (x - chunk mean)^2; the partial becomes (chunk mean, -m2) - the sign marks it
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { mu[k] = smean[(o * 8 + k) / cpg]; a0[k] = 0.f; }
+  for (int r = r0 + rp; r < r1; r += p.RP) {
+    float f[8];
+    gn_load(p, (long)b * p.HW + r, o, f);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { const float d = f[k] - mu[k]; a0[k] += d * d; }
+  }
+  gn_octet_sum(red, a0, p, rp, o);
+  for (int g = threadIdx.x; g < p.G; g += blockDim.x) {
+    float m2 = 0.f;
+    for (int c = g * cpg; c < (g + 1) * cpg; ++c) m2 += red[c];
+    float* dst = p.part + (((long)b * p.chunks + chunk) * p.G + g) * 2;
+    dst[0] = smean[g];
+    dst[1] = -fmaxf(m2, 0.f);
   }
 }
 template <bool BWD>
@@ -957,26 +1009,51 @@ __global__ void gn_apply_kernel(const GnDev p) {
   const int cpg = p.C / p.G;
   // the image's statistics from the chunks' partials: thread (g, part) sums every PARTS-th chunk of group g, LDS combines the parts in a
   // fixed order (every workgroup of the image gets the same bits)
-  float* parts = stat + 2 * p.G;                           // [PARTS][G][2]
+  // forward: a partial is (sum x, sum x^2), or (chunk mean, -m2) from a chunk that was summed again, centred.  Sums alone: they
+  // are added up as they are (s0, s1).  One centred chunk in the group (rare): its thread merges all chunks as (mean, m2) with
+  // Chan's formula, in chunk order.
+  float* parts = stat + 2 * p.G;                           // [PARTS][G][3]: s0, s1, centred chunk seen
   const int PARTS = max(1, (int)blockDim.x / p.G);
   for (int idx = threadIdx.x; idx < PARTS * p.G; idx += blockDim.x) {
     const int g = idx % p.G, part = idx / p.G;
-    float s0 = 0.f, s1 = 0.f;
+    float s0 = 0.f, s1 = 0.f, centred = 0.f;
     for (int ch = part; ch < p.chunks; ch += PARTS) {
       const float* src = p.part + (((long)b * p.chunks + ch) * p.G + g) * 2;
       s0 += src[0];
       s1 += src[1];
+      if (!BWD && signbit(src[1])) centred = 1.f;
     }
-    parts[(part * p.G + g) * 2] = s0;
-    parts[(part * p.G + g) * 2 + 1] = s1;
+    parts[(part * p.G + g) * 3] = s0;
+    parts[(part * p.G + g) * 3 + 1] = s1;
+    parts[(part * p.G + g) * 3 + 2] = centred;
   }
   __syncthreads();
   for (int g = threadIdx.x; g < p.G; g += blockDim.x) {
-    float s0 = 0.f, s1 = 0.f;
-    for (int part = 0; part < PARTS; ++part) { s0 += parts[(part * p.G + g) * 2]; s1 += parts[(part * p.G + g) * 2 + 1]; }
+    float s0 = 0.f, s1 = 0.f, centred = 0.f;
+    for (int part = 0; part < PARTS; ++part) {
+      s0 += parts[(part * p.G + g) * 3];
+      s1 += parts[(part * p.G + g) * 3 + 1];
+      centred += parts[(part * p.G + g) * 3 + 2];
+    }
     const float n = (float)p.HW * cpg;
     if (!BWD) {
-      const float mu = s0 / n, var = fmaxf(s1 / n - mu * mu, 0.f), rs = rsqrtf(var + p.eps);
+      float mu = s0 / n, var = fmaxf(s1 / n - mu * mu, 0.f);
+      if (centred > 0.f) {
+        float cm = 0.f, cm2 = 0.f, cnt = 0.f;
+        for (int ch = 0; ch < p.chunks; ++ch) {
+          const float* src = p.part + (((long)b * p.chunks + ch) * p.G + g) * 2;
+          const float nb = (float)(min(p.HW, (ch + 1) * p.rows_per_chunk) - ch * p.rows_per_chunk) * cpg;
+          const bool cen = signbit(src[1]);
+          const float mb = cen ? src[0] : src[0] / nb, m2b = cen ? -src[1] : fmaxf(src[1] - src[0] * mb, 0.f);
+          const float d = mb - cm, nt = cnt + nb;
+          cm += d * (nb / nt);
+          cm2 += m2b + d * d * (cnt * nb / nt);
+          cnt = nt;
+        }
+        mu = cm;
+        var = fmaxf(cm2 / n, 0.f);
+      }
+      const float rs = rsqrtf(var + p.eps);
       stat[2 * g] = mu;
       stat[2 * g + 1] = rs;
       if (chunk == 0) { p.mean[b * p.G + g] = mu; p.rstd[b * p.G + g] = rs; }     // kept for the backward pass
@@ -1339,10 +1416,10 @@ static int gn_run(const gad_groupnorm_args* a, hipStream_t st, const char* who) 
   if (gn_check(a, who)) return 1;
   const GnDev d = gn_dev(a);
   const dim3 grid(d.chunks, d.B), block(d.NO * d.RP);
-  hipLaunchKernelGGL(gn_part_kernel<BWD>, grid, block, (size_t)d.RP * d.NO * 16 * 4, st, d);
+  hipLaunchKernelGGL(gn_part_kernel<BWD>, grid, block, ((size_t)d.RP * d.NO * 16 + d.G + 1) * 4, st, d);
   GAD_LAUNCH_CHECK("h_gn_part");
   const int parts = d.NO * d.RP / d.G > 0 ? d.NO * d.RP / d.G : 1;
-  hipLaunchKernelGGL(gn_apply_kernel<BWD>, grid, block, (size_t)(1 + parts) * d.G * 2 * 4, st, d);
+  hipLaunchKernelGGL(gn_apply_kernel<BWD>, grid, block, (size_t)(2 + 3 * parts) * d.G * 4, st, d);
   GAD_LAUNCH_CHECK("h_gn_apply");
   return 0;
 }

@@ -53,9 +53,24 @@ __device__ __forceinline__ const float* gn_src(const float* x, const float* x2, 
   return x2 + ((long)b * HW) * (C - C1) + (c0 - C1);
 }
 
+// Chunk moments.  `SS - S mean` in fp32 cancels where a group's mean lies far from zero against its spread (|mean| / std = 100
+// costs rstd four digits, and real activations have such groups; tests/test_gpu_norm_conditioning.py,
+// profiles/gn_conditioning.txt).  The cancellation shows in the result itself: SS / m2 = 1 + (mean / std)^2 is the factor by
+// which the sums' rounding is magnified.  Up to GN_COND the one-sweep moments stand (|mean| / std < 3.9: at most 4 bits, inside
+// what another summation order costs); beyond it the workgroup sweeps its chunk a second time, out of L2, for the centred sums.
+// (GN_COND: gad_common.h)
+// The same measure for the output: y = x scale + (beta - mean scale) rounds at the size of mean scale, so a channel quad with
+// (mean rstd)^2 > GN_COND - 1 is written as (x - mean) scale + beta (a constant group then gives beta exactly).
+__device__ __forceinline__ bool gn_far_mean(const f32x4& mu, const f32x4& rs) {
+  const f32x4 t = (mu * rs) * (mu * rs);
+  return !(fmaxf(fmaxf(t[0], t[1]), fmaxf(t[2], t[3])) <= GN_COND - 1.f);
+}
 __global__ __launch_bounds__(NT) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ part, Geo g,
                                                       const float* __restrict__ x2, int C1) {
   __shared__ float red[2 * MAXC];  // [rows_par][C] sums then sumsqs; rows_par*C <= max(1024, C)
+  __shared__ float s_mean[256];
+  __shared__ int s_ill;
+  if (threadIdx.x == 0) s_ill = 0;              // (the __syncthreads() ahead of the group loop orders it)
   int b = blockIdx.x / g.nch, ch = blockIdx.x - b * g.nch;
   int p0 = ch * g.ppc, p1 = min(g.HW, p0 + g.ppc);
   int tid = threadIdx.x;
@@ -100,6 +115,54 @@ __global__ __launch_bounds__(NT) void gn_stats_kernel(const float* __restrict__ 
     float* o = part + (((long)b * g.nch + ch) * g.G + grp) * 2;
     o[0] = mean;
     o[1] = m2;
+    s_mean[grp] = mean;
+    if (!(SS <= GN_COND * m2)) s_ill = 1;       // SS - S mean lost more than log2(GN_COND) bits: this chunk is summed again, centred
+  }
+  __syncthreads();
+  if (!s_ill) return;                           // (block-uniform)
+  // sum (x - mean) and sum (x - mean)^2 about the first sweep's mean (corrected two-pass algorithm; the chunk comes from L2)
+  if (prow < g.rows_par) {
+    for (int cq = cfirst; cq < g.C4; cq += g.tpr) {
+      const int c0 = cq * 4;
+      const f32x4 mu = {s_mean[c0 / g.cpg], s_mean[(c0 + 1) / g.cpg], s_mean[(c0 + 2) / g.cpg], s_mean[(c0 + 3) / g.cpg]};
+      f32x4 rr = {0, 0, 0, 0}, ss = {0, 0, 0, 0};
+      int ldx;
+      const float* xb = gn_src(x, x2, C1, g.C, g.HW, b, c0, &ldx);
+      const int R = g.rows_par;
+      int p = p0 + prow;
+      for (; p + 3 * R < p1; p += 4 * R) {
+        f32x4 d0 = *reinterpret_cast<const f32x4*>(xb + (long)p * ldx) - mu;
+        f32x4 d1 = *reinterpret_cast<const f32x4*>(xb + (long)(p + R) * ldx) - mu;
+        f32x4 d2 = *reinterpret_cast<const f32x4*>(xb + (long)(p + 2 * R) * ldx) - mu;
+        f32x4 d3 = *reinterpret_cast<const f32x4*>(xb + (long)(p + 3 * R) * ldx) - mu;
+        rr += (d0 + d1) + (d2 + d3);
+        ss += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+      }
+      for (; p < p1; p += R) {
+        f32x4 d = *reinterpret_cast<const f32x4*>(xb + (long)p * ldx) - mu;
+        rr += d;
+        ss += d * d;
+      }
+      float* r0 = red + prow * g.C + c0;
+      float* r1 = red + g.rows_par * g.C + prow * g.C + c0;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { r0[e] = rr[e]; r1[e] = ss[e]; }
+    }
+  }
+  __syncthreads();
+  for (int grp = tid; grp < g.G; grp += NT) {
+    float R1 = 0.f, M2 = 0.f;
+    for (int r = 0; r < g.rows_par; ++r)
+      for (int c = grp * g.cpg; c < (grp + 1) * g.cpg; ++c) {
+        R1 += red[r * g.C + c];
+        M2 += red[g.rows_par * g.C + r * g.C + c];
+      }
+    // S / n is the chunk's mean to a few ulp of a long fp32 sum only, and Chan's merge wants the chunk's own mean:
+    // mean = S / n + R1 / n, m2 = sum (x - S / n)^2 - R1^2 / n (a small correction)
+    const float n = (float)((p1 - p0) * g.cpg), corr = R1 / n;
+    float* o = part + (((long)b * g.nch + ch) * g.G + grp) * 2;
+    o[0] = s_mean[grp] + corr;                  // (every group of such a chunk takes the centred moments)
+    o[1] = fmaxf(M2 - R1 * corr, 0.f);
   }
 }
 
@@ -150,6 +213,7 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const float* __restrict__ 
       rs[e] = s_rstd[grp];
     }
     f32x4 scale = rs * ga, shift = be - mu * scale;
+    const bool far = gn_far_mean(mu, rs);
     long base = ((long)b * g.HW) * g.C + c0;
     int ldx;
     const float* xb = gn_src(x, x2, C1, g.C, g.HW, b, c0, &ldx);
@@ -161,7 +225,7 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const float* __restrict__ 
       for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(xb + (long)(p + u * R) * ldx);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
-        f32x4 z = v[u] * scale + shift;
+        f32x4 z = far ? (v[u] - mu) * scale + be : v[u] * scale + shift;
         if (silu) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) z[e] = silu_f(z[e]);
@@ -171,7 +235,7 @@ __global__ __launch_bounds__(NT) void gn_apply_kernel(const float* __restrict__ 
     }
     for (; p < p1; p += R) {
       f32x4 v = *reinterpret_cast<const f32x4*>(xb + (long)p * ldx);
-      f32x4 z = v * scale + shift;
+      f32x4 z = far ? (v - mu) * scale + be : v * scale + shift;
       if (silu) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[e] = silu_f(z[e]);
@@ -270,8 +334,8 @@ __global__ __launch_bounds__(NTH) void gn_slab_kernel(const float* __restrict__ 
   } else {
     slab_reduce(red, (acc[0] + acc[1]) + (acc[2] + acc[3]), s, pl, act);
   }
+  float S = 0.f;
   if (tid < s.gps) {
-    float S = 0.f;
     if (PERCH) for (int j = 0; j < s.cpg; ++j) S += chan[tid * s.cpg + j];
     else for (int j = 0; j < s.qpg; ++j) S += red[tid * s.qpg + j];
     s_mean[tid] = S * inv_n;
@@ -298,6 +362,13 @@ __global__ __launch_bounds__(NTH) void gn_slab_kernel(const float* __restrict__ 
     if (PERCH) for (int j = 0; j < s.cpg; ++j) SS += chan[tid * s.cpg + j];
     else for (int j = 0; j < s.qpg; ++j) SS += red[tid * s.qpg + j];
     float rs = rsqrtf(SS * inv_n + eps);
+    // a mean far from zero against the spread is divided out, not multiplied by 1 / n (a constant group's mean is that
+    // constant), and the squares, taken about S (1 / n), are moved to it: sum (x - m)^2 = sum (x - mean)^2 + n (m - mean)^2
+    if (!((s_mean[tid] * rs) * (s_mean[tid] * rs) <= GN_COND - 1.f)) {
+      const float md = S / (float)((long)s.HW * s.cpg), d = s_mean[tid] - md;
+      rs = rsqrtf(fmaxf(SS * inv_n - d * d, 0.f) + eps);
+      s_mean[tid] = md;
+    }
     s_rstd[tid] = rs;
     mean_out[b * s.G + sl * s.gps + tid] = s_mean[tid];
     rstd_out[b * s.G + sl * s.gps + tid] = rs;
@@ -305,15 +376,22 @@ __global__ __launch_bounds__(NTH) void gn_slab_kernel(const float* __restrict__ 
   __syncthreads();
   if (!act) return;
   f32x4 rs;
-  if (PERCH) rs = f32x4{s_rstd[gi[0]], s_rstd[gi[1]], s_rstd[gi[2]], s_rstd[gi[3]]};
-  else { const float r1 = s_rstd[q / s.qpg]; rs = f32x4{r1, r1, r1, r1}; }
+  if (PERCH) {
+    rs = f32x4{s_rstd[gi[0]], s_rstd[gi[1]], s_rstd[gi[2]], s_rstd[gi[3]]};
+    mu = f32x4{s_mean[gi[0]], s_mean[gi[1]], s_mean[gi[2]], s_mean[gi[3]]};
+  } else {
+    const float r1 = s_rstd[q / s.qpg], m1 = s_mean[q / s.qpg];
+    rs = f32x4{r1, r1, r1, r1};
+    mu = f32x4{m1, m1, m1, m1};
+  }
   f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0), be = *reinterpret_cast<const f32x4*>(beta + c0);
   f32x4 scale = ga * rs, shift = be - scale * mu;
+  const bool far = gn_far_mean(mu, rs);
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     int p = pl + i * s.PL;
     if (p < s.HW) {
-      f32x4 z = v[i] * scale + shift;
+      f32x4 z = far ? (v[i] - mu) * scale + be : v[i] * scale + shift;
       if (silu) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) z[e] = silu_f(z[e]);
@@ -405,8 +483,8 @@ __global__ __launch_bounds__(512) void gn_wino4_kernel(const float* __restrict__
   for (int i = 0; i < NV; ++i) acc += v[i];
   const float inv_n = 1.f / (float)((long)s.HW * s.cpg);
   slab_reduce(red, (acc[0] + acc[1]) + (acc[2] + acc[3]), s, pl, act);
+  float S = 0.f;
   if (tid < s.gps) {
-    float S = 0.f;
     for (int j = 0; j < s.qpg; ++j) S += red[tid * s.qpg + j];
     s_mean[tid] = S * inv_n;
   }
@@ -425,6 +503,11 @@ __global__ __launch_bounds__(512) void gn_wino4_kernel(const float* __restrict__
     float SS = 0.f;
     for (int j = 0; j < s.qpg; ++j) SS += red[tid * s.qpg + j];
     float rs = rsqrtf(SS * inv_n + eps);
+    if (!((s_mean[tid] * rs) * (s_mean[tid] * rs) <= GN_COND - 1.f)) {      // as gn_slab_kernel: the divided mean, the squares moved to it
+      const float md = S / (float)((long)s.HW * s.cpg), d = s_mean[tid] - md;
+      rs = rsqrtf(fmaxf(SS * inv_n - d * d, 0.f) + eps);
+      s_mean[tid] = md;
+    }
     s_rstd[tid] = rs;
     mean_out[b * s.G + sl * s.gps + tid] = s_mean[tid];
     rstd_out[b * s.G + sl * s.gps + tid] = rs;
@@ -432,15 +515,16 @@ __global__ __launch_bounds__(512) void gn_wino4_kernel(const float* __restrict__
   __syncthreads();
   f32x4* img4 = reinterpret_cast<f32x4*>(gn_img);
   if (act) {
-    const float r1 = s_rstd[q / s.qpg];
-    const f32x4 rs = f32x4{r1, r1, r1, r1};
+    const float r1 = s_rstd[q / s.qpg], m2 = s_mean[q / s.qpg];
+    const f32x4 rs = f32x4{r1, r1, r1, r1}, mu2 = f32x4{m2, m2, m2, m2};
     const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + c0), be = *reinterpret_cast<const f32x4*>(beta + c0);
-    const f32x4 scale = ga * rs, shift = be - scale * mu;
+    const f32x4 scale = ga * rs, shift = be - scale * mu2;
+    const bool far = gn_far_mean(mu2, rs);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       int p = pl + i * s.PL;
       if (p < s.HW) {
-        f32x4 z = v[i] * scale + shift;
+        f32x4 z = far ? (v[i] - mu2) * scale + be : v[i] * scale + shift;
         if (silu) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) z[e] = silu_f(z[e]);
