@@ -133,9 +133,9 @@ class ResnetBlock2D(nn.Module):
             sc = self.conv_shortcut(x, x2=x2) if self.conv_shortcut is not None else x
             return ops.gn_silu_conv3x3_raw(h, None, n2.weight, n2.bias, n2.num_groups, n2.eps, self.conv2.weight, self.conv2.bias,
                                            residual=sc)
-        # training: each norm -> silu -> conv half is one autograd node (ops.GnSiluConv3x3Fn): on the Winograd F(4x4) route the norm
-        # writes the convolution's transformed input, which is also what the weight gradient reads - the normalised activation
-        # itself never exists; conv + bias + temb add / skip add are the convolution's epilogue either way
+        # training: each norm -> silu -> conv half is one autograd node (ops.GnSiluConv3x3Fn) over the two ordinary launches: the
+        # normalised activation is saved only for a trainable weight, whose gradient reads the transformed input an F(4x4) forward
+        # launch kept; conv + bias + temb add / skip add are the convolution's epilogue
         n1, n2 = self.norm1, self.norm2
         if x2 is None:
             h, x = ops.gn_silu_conv3x3(x, n1.weight, n1.bias, n1.num_groups, n1.eps, self.conv1.weight, self.conv1.bias,

@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from typing import Optional
 
 import torch
@@ -214,11 +213,6 @@ OUT_ALLOC_DT = None          # the same for the half path's outputs: (shape, dev
 
 
 ROUTE_STATS = None         # a dict while tools/wino_route_stats.py counts which 3x3 launches take a Winograd route and who made their V
-# Training: GroupNorm writing the Winograd input image itself (as in sampling).  OFF by default: at B = 128 it is no faster than GroupNorm + the
-# route's input transform (31.2 vs 31.3 ms per step: the activation round trip stays in the Infinity Cache) and it changes fp32 rounding, i.e. the
-# 1000-step trajectory; with it off the training step's results are bit-identical to the separate launches'.  GAD_TRAIN_GN_WINO=1 switches it on.
-TRAIN_GN_WINO = [os.environ.get("GAD_TRAIN_GN_WINO", "0") == "1"]
-KEEP_WINO_V = [os.environ.get("GAD_KEEP_WINO_V", "1") != "0"]      # training: the forward's Winograd input image serves the weight gradient
 
 
 def _scratch(kind, nbytes, device):
@@ -244,7 +238,8 @@ def gemm_raw(A, B, Cout, a_mode, b_mode, M, N, K, lda, ldb, ldc, *, geom: Option
     `force_f32`: exact fp32 products whatever the process-wide operand precision (small parameter-gradient products).
     `wino_input(V)`: the caller supplies the F(4x4) Winograd input transform itself (GroupNorm writing V directly,
     `gn_silu_conv3x3_raw`): if the planner puts this launch on an F(4x4) route the callback is run on the route's scratch and
-    the convolution starts behind its input stage (-> True); on any other route nothing is launched (-> False)."""
+    the convolution starts behind its input stage; on any other route nothing is launched.
+    -> False in exactly that case (`wino_input` given and the planner chose another route); True after every launch."""
     lib = _capi.load()
     ws = workspace(A.device)
     a = GemmArgs()
@@ -295,8 +290,6 @@ def gemm_raw(A, B, Cout, a_mode, b_mode, M, N, K, lda, ldb, ldc, *, geom: Option
                 a.flags |= _capi.GEMM_WINO_SKIP_INPUT
         else:
             a.flags &= ~_capi.GEMM_WINO_WGRAD
-    if isinstance(B, _ShapeOnly) and not (a.flags & _capi.GEMM_WINO_SKIP_INPUT):
-        return False                 # the activation exists only as the kept image and this launch would not read it: the caller re-makes it
     if wino_input is not None:
         if lib.gad_gemm_kernel_id(C.byref(a)) != 6 or not a.wino_ws:
             return False
@@ -733,9 +726,13 @@ def conv2d_dgrad_raw(dy, w, x_shape, stride=1, pad=(1, 1, 1, 1), upsample=False,
     g = ConvGeom(Ho, Wo, Cout, Cout, He, We, KH, KW, stride, pad[0], pad[2], 0)
     gemm_raw(dy, wk, dxe, A_CONVT, B_WDGRAD, Bn * He * We, Cin, KH * KW * Cout, 0, 0, Cin, geom=g,
              tile_hint=tile_hint, splitk_hint=splitk_hint)
-    if not upsample:
-        return dxe
-    dx = torch.empty((Bn, H, W, Cin), device=dy.device, dtype=torch.float32)
+    return _upsample2x_bwd(dxe, x_shape) if upsample else dxe
+
+
+def _upsample2x_bwd(dxe, x_shape):
+    """dxe [B,2H,2W,C], the gradient on the nearest-2x grid an upsample-fused conv ran on -> dx [B,H,W,C]: sums the 2 x 2 replicas."""
+    Bn, H, W, Cin = x_shape
+    dx = torch.empty((Bn, H, W, Cin), device=dxe.device, dtype=torch.float32)
     check(_capi.load().gad_upsample2x_bwd(dxe.data_ptr(), dx.data_ptr(), Bn, H, W, Cin, _stream()), "gad_upsample2x_bwd")
     return dx
 
@@ -745,8 +742,7 @@ def conv2d_wgrad_raw(dy, x, w_like, stride=1, pad=(1, 1, 1, 1), upsample=False, 
     [Cout,Cin,KH,KW] view with that storage to write into (flat gradient slot); `wino_v` = the scratch the forward launch of
     this convolution kept (`conv2d_fwd_raw(keep_v=)`): the Winograd form then reads the transformed input from it."""
     _req(dy, "conv dy")
-    if not isinstance(x, _ShapeOnly):
-        _req(x, "conv x")
+    _req(x, "conv x")
     Bn, H, W, Cin = x.shape
     Cout, _, KH, KW = w_like.shape
     _, Ho, Wo, _ = dy.shape
@@ -760,9 +756,8 @@ def conv2d_wgrad_raw(dy, x, w_like, stride=1, pad=(1, 1, 1, 1), upsample=False, 
             and Ho % 4 == 0 and Wo % 4 == 0 and OPERAND_PRECISION[0] == 0 and not KERNEL_FLAGS.get("no_wino4")
             and not KERNEL_FLAGS["gemm"] & (_capi.GEMM_NO_WINO | _capi.GEMM_NO_PATCH | _capi.GEMM_SCALAR_EPILOGUE | _capi.GEMM_TAP_MAJOR_K
                                             | _capi.GEMM_GENERAL_LOADERS))
-    if gemm_raw(dy, x, dwk, A_MC, B_CONV, Cout, KH * KW * Cin, Bn * Ho * Wo, Cout, 0, KH * KW * Cin, geom=g,
-                tile_hint=tile_hint, splitk_hint=splitk_hint, wino_wgrad=wino, wino_v=wino_v) is False:
-        return None                  # (x given as a shape and no Winograd launch on the kept image: nothing ran)
+    gemm_raw(dy, x, dwk, A_MC, B_CONV, Cout, KH * KW * Cin, Bn * Ho * Wo, Cout, 0, KH * KW * Cin, geom=g,
+             tile_hint=tile_hint, splitk_hint=splitk_hint, wino_wgrad=wino, wino_v=wino_v)
     return dwk.permute(0, 3, 1, 2)
 
 
@@ -818,6 +813,27 @@ def _param_grad(param, compute):
     return None
 
 
+def _conv_backward(ctx, dy, x, x_shape, w, stride, pad, upsample, has, need):
+    """Backward of y = conv(x) + bias + rowadd[b] + residual for Conv2dFn and GnSiluConv3x3Fn -> (dx, dw, d bias, d rowadd,
+    d residual).  `has` / `need`: which of (bias, rowadd, residual) the forward had, and which of
+    (x, w, bias, rowadd, residual) want a gradient; `x` (the conv's input) is read only for the weight gradient, which takes the
+    transformed input the forward launch kept (`ctx.wino_v`) in its Winograd form."""
+    dy = dy.contiguous()
+    dx = None
+    if need[0]:
+        if dgrad_as_forward(w, stride, pad):
+            dx = conv2d_fwd_raw(dy, rotated_weight(w), None)
+            if upsample:
+                dx = _upsample2x_bwd(dx, x_shape)
+        else:
+            dx = conv2d_dgrad_raw(dy, w, x_shape, stride, pad, upsample)
+    V, ctx.wino_v = ctx.wino_v, None
+    dw = _param_grad(w, lambda o: conv2d_wgrad_raw(dy, x, w, stride, pad, upsample, out=o, wino_v=V)) if need[1] else None
+    db, dr = _conv_epilogue_grads(dy, ctx.bias_ref, has[0] and need[2], has[1] and need[3])
+    dres = dy if (has[2] and need[4]) else None
+    return dx, dw, db, dr, dres
+
+
 class Conv2dFn(torch.autograd.Function):
     """y = conv(x) + bias + rowadd[b] (time-embedding add) + residual, all fused in the
     contraction epilogue (ResnetBlock2D / Downsample2D / Upsample2D)."""
@@ -826,10 +842,10 @@ class Conv2dFn(torch.autograd.Function):
     def forward(ctx, x, w, bias, rowadd, residual, stride, pad, upsample):
         ctx.save_for_backward(x, w)
         ctx.bias_ref = bias
-        ctx.cfg = (stride, pad, upsample, bias is not None, rowadd is not None, residual is not None)
+        ctx.cfg = (stride, pad, upsample, (bias is not None, rowadd is not None, residual is not None))
         # an F(4x4) forward launch leaves the transformed input V in its scratch: kept for the weight gradient, which would make
-        # the same image from x again (KEEP_WINO_V off: the scratch is dropped after the launch as before)
-        keep = [] if (KEEP_WINO_V[0] and ctx.needs_input_grad[1]) else None
+        # the same image from x again
+        keep = [] if ctx.needs_input_grad[1] else None
         y = conv2d_fwd_raw(x, w, bias, stride, pad, upsample, rowadd, residual, keep_v=keep)
         ctx.wino_v = keep[0] if keep else None
         return y
@@ -837,25 +853,8 @@ class Conv2dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        stride, pad, upsample, has_b, has_r, has_res = ctx.cfg
-        dy = dy.contiguous()
-        Bn, Ho, Wo, Cout = dy.shape
-        dx = None
-        if ctx.needs_input_grad[0]:
-            if dgrad_as_forward(w, stride, pad):
-                dx = conv2d_fwd_raw(dy, rotated_weight(w), None)
-                if upsample:                         # the conv ran on the nearest-2x grid: sum the 2 x 2 replicas
-                    dxe, dx = dx, torch.empty(x.shape, device=dy.device, dtype=torch.float32)
-                    check(_capi.load().gad_upsample2x_bwd(dxe.data_ptr(), dx.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
-                                                          x.shape[3], _stream()), "gad_upsample2x_bwd")
-            else:
-                dx = conv2d_dgrad_raw(dy, w, x.shape, stride, pad, upsample)
-        dw = _param_grad(w, lambda o: conv2d_wgrad_raw(dy, x, w, stride, pad, upsample, out=o, wino_v=ctx.wino_v)) \
-            if ctx.needs_input_grad[1] else None
-        ctx.wino_v = None
-        db, dr = _conv_epilogue_grads(dy, ctx.bias_ref, has_b and ctx.needs_input_grad[2], has_r and ctx.needs_input_grad[3])
-        dres = dy if (has_res and ctx.needs_input_grad[4]) else None
-        return dx, dw, db, dr, dres, None, None, None
+        stride, pad, upsample, has = ctx.cfg
+        return (*_conv_backward(ctx, dy, x, x.shape, w, stride, pad, upsample, has, ctx.needs_input_grad[:5]), None, None, None)
 
 
 def _conv_epilogue_grads(dy, bias, need_bias, need_rowadd):
@@ -872,74 +871,38 @@ def _conv_epilogue_grads(dy, bias, need_bias, need_rowadd):
 
 
 class GnSiluConv3x3Fn(torch.autograd.Function):
-    """Training form of a ResnetBlock2D half: (y [, alias of x]) = (conv3x3(SiLU(GroupNorm(x))) + bias + rowadd[b] + residual [, x]).
-    Where the convolution takes an F(4x4) Winograd route and the norm has a plan for it, GroupNorm writes the route's
-    transformed input V (`gad_groupnorm_silu_wino4`, as in sampling: `gn_silu_conv3x3_raw`) and V is ALL that is kept of the
-    normalised activation: the weight gradient reads it (`GAD_GEMM_WINO_SKIP_INPUT`), the data gradient and the norm's backward
-    never needed it - one pass less over the activation forward and backward, and no input-transform launch on either side.
-    On any other route: the two ordinary launches, the activation kept.  Backward = Conv2dFn's then GroupNormSiluFn's kernels."""
+    """Training form of a ResnetBlock2D half: (y [, alias of x]) = (conv3x3(SiLU(GroupNorm(x))) + bias + rowadd[b] + residual [, x])
+    as ONE autograd node over the two ordinary launches, `gad_groupnorm_silu_fwd` then the convolution: the normalised
+    activation h is saved only where the weight wants a gradient (a frozen weight: nothing reads it again), and an F(4x4)
+    forward launch's transformed input is kept for that weight gradient as in Conv2dFn.  Results are bit-identical to the two
+    separate nodes'.  Backward = Conv2dFn's then GroupNormSiluFn's kernels."""
 
     @staticmethod
     def forward(ctx, x, gamma, beta, w, bias, rowadd, residual, G, eps, bypass):
         _req(x, "groupnorm x")
-        Bn, H, W, Cin = x.shape
-        lib = _capi.load()
+        Bn = x.shape[0]
         mean = torch.empty((Bn, G), device=x.device, dtype=torch.float32)
         rstd = torch.empty_like(mean)
         keep = [] if ctx.needs_input_grad[3] else None
-        y = h = None
-        if not (OPERAND_PRECISION[0] != 0 or KERNEL_FLAGS["gn"] or KERNEL_FLAGS.get("no_gn_wino") or H % 4 or W % 4 or not KEEP_WINO_V[0]
-                or keep is None or not TRAIN_GN_WINO[0]):
-            a = GroupNormArgs()
-            a.x, a.gamma, a.beta, a.mean, a.rstd = x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-            a.B, a.HW, a.C, a.G, a.eps, a.silu = Bn, H * W, Cin, G, eps, 1
-            if lib.gad_groupnorm_wino4_ok(C.byref(a), W):
-                def fill(V):
-                    check(lib.gad_groupnorm_silu_wino4(C.byref(a), V.data_ptr(), W, _stream()), "gad_groupnorm_silu_wino4")
-                y = conv2d_fwd_raw(_ShapeOnly(x, (Bn, H, W, Cin)), w, bias, 1, (1, 1, 1, 1), False, rowadd=rowadd, residual=residual,
-                                   wino_input=fill, keep_v=keep)
-                if y is None:
-                    keep.clear()                         # (planned on another route: nothing was launched)
-        if y is None:
-            h = torch.empty_like(x)
-            check(lib.gad_groupnorm_silu_fwd(C.byref(_gn_args(x, h, gamma, beta, mean, rstd, G, eps, True)), _stream()), "gad_groupnorm_silu_fwd")
-            y = conv2d_fwd_raw(h, w, bias, 1, (1, 1, 1, 1), False, rowadd=rowadd, residual=residual, keep_v=keep)
+        h = torch.empty_like(x)
+        check(_capi.load().gad_groupnorm_silu_fwd(C.byref(_gn_args(x, h, gamma, beta, mean, rstd, G, eps, True)), _stream()),
+              "gad_groupnorm_silu_fwd")
+        y = conv2d_fwd_raw(h, w, bias, 1, (1, 1, 1, 1), False, rowadd=rowadd, residual=residual, keep_v=keep)
         ctx.save_for_backward(x, gamma, beta, mean, rstd, w, h if keep is not None else None)     # (a frozen weight: nothing reads h again)
         ctx.wino_v = keep[0] if keep else None
         ctx.bias_ref = bias
-        ctx.cfg = (G, eps, bias is not None, rowadd is not None, residual is not None)
+        ctx.cfg = (G, eps, (bias is not None, rowadd is not None, residual is not None))
         return (y, x.view_as(x)) if bypass else y
 
     @staticmethod
     def backward(ctx, dy, dbypass=None):
         x, gamma, beta, mean, rstd, w, h = ctx.saved_tensors
-        G, eps, has_b, has_r, has_res = ctx.cfg
+        G, eps, has = ctx.cfg
         need = ctx.needs_input_grad
         if dy is None:                                   # only the alias of x was used downstream
             return (dbypass, *([None] * 9))
-        dy = dy.contiguous()
-        V, ctx.wino_v = ctx.wino_v, None
-        dh = None
-        if need[0] or need[1] or need[2]:
-            dh = conv2d_fwd_raw(dy, rotated_weight(w), None) if dgrad_as_forward(w, 1, (1, 1, 1, 1)) \
-                else conv2d_dgrad_raw(dy, w, x.shape, 1, (1, 1, 1, 1), False)
-        dw = None
-        if need[3]:
-            def wgrad(o):
-                r = None
-                if h is None:                            # the activation exists only as V: the Winograd form on it
-                    r = conv2d_wgrad_raw(dy, _ShapeOnly(x, x.shape), w, 1, (1, 1, 1, 1), False, tile_hint=8, out=o, wino_v=V)
-                if r is None:
-                    hh = h
-                    if hh is None:                       # (the library declined: make the activation again)
-                        hh = torch.empty_like(x)
-                        check(_capi.load().gad_groupnorm_silu_fwd(C.byref(_gn_args(x, hh, gamma, beta, mean.clone(), rstd.clone(), G, eps, True)),
-                                                                  _stream()), "gad_groupnorm_silu_fwd")
-                    r = conv2d_wgrad_raw(dy, hh, w, 1, (1, 1, 1, 1), False, out=o, wino_v=V)
-                return r
-            dw = _param_grad(w, wgrad)
-        db, dr = _conv_epilogue_grads(dy, ctx.bias_ref, has_b and need[4], has_r and need[5])
-        dres = dy if (has_res and need[6]) else None
+        dh, dw, db, dr, dres = _conv_backward(ctx, dy, h, x.shape, w, 1, (1, 1, 1, 1), False, has,
+                                              (need[0] or need[1] or need[2], *need[3:7]))
         dx = dgamma = dbeta = None
         if dh is not None:
             dx, dgamma, dbeta = _gn_backward(x, gamma, beta, mean, rstd, G, eps, True, dh, dbypass, need[1] or need[2])
@@ -950,7 +913,8 @@ class GnSiluConv3x3Fn(torch.autograd.Function):
 
 def gn_silu_conv3x3(x, gamma, beta, G, eps, w, bias, rowadd=None, residual=None, bypass=False):
     """Differentiable conv3x3(SiLU(GroupNorm(x))) + bias + rowadd + residual (GnSiluConv3x3Fn); with `bypass` also an alias of
-    x for the block's residual branch (as `group_norm_bypass`).  Half-precision activations and odd shapes: the two separate ops."""
+    x for the block's residual branch (as `group_norm_bypass`).  Bit-identical to `group_norm` then `conv2d`, which half-precision
+    activations and odd shapes take."""
     if x.dtype == torch.bfloat16 or tuple(w.shape[2:]) != (3, 3) or w.shape[1] != x.shape[-1] or x.ndim != 4:
         if bypass:
             h, x = group_norm_bypass(x, gamma, beta, G, eps, True)

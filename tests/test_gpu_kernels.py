@@ -332,27 +332,19 @@ def test_conv_wgrad_winograd_takes_the_forward_input_image(ops, B, Cin, Cout, H,
     with ops.kernel_flags(no_wino=True):
         ops.conv2d_fwd_raw(xg, wg, None, 1, (1, 1, 1, 1), ups, keep_v=none)
     assert none == []
-    # through autograd (planner's routes): the same gradient with and without the kept image
-    grads = []
-    for on in (True, False):
-        ops.KEEP_WINO_V[0] = on
-        try:
-            wp = wg.clone().requires_grad_(True)
-            ops.conv2d(xg, wp, None, None, None, 1, (1, 1, 1, 1), ups).backward(dyg)
-            grads.append(wp.grad)
-        finally:
-            ops.KEEP_WINO_V[0] = True
-    assert torch.equal(grads[0], grads[1])
+    # through autograd (planner's routes): the gradient from the kept image equals the one from the re-transformed input
+    wp = wg.clone().requires_grad_(True)
+    ops.conv2d(xg, wp, None, None, None, 1, (1, 1, 1, 1), ups).backward(dyg)
+    assert torch.equal(wp.grad, ops.conv2d_wgrad_raw(dyg, xg, wg, 1, (1, 1, 1, 1), ups))
 
 
 @pytest.mark.parametrize("B,C,Cout,H,W,G,bypass", [(8, 128, 128, 32, 32, 32, True), (4, 64, 128, 16, 16, 16, False), (3, 256, 256, 8, 8, 32, True),
                                                     (2, 32, 64, 6, 6, 8, False), (2, 128, 128, 64, 64, 32, True)])
 def test_gn_silu_conv3x3_training_node(ops, B, C, Cout, H, W, G, bypass):
-    """ResnetBlock2D's training halves as ONE autograd node (ops.GnSiluConv3x3Fn: GroupNorm writes the Winograd route's transformed
-    input, kept for the weight gradient; the normalised activation never exists) against the two separate nodes: every gradient
-    (input incl. the bypass alias's, norm affine, weight, bias, time-embedding row, residual) bit for bit by default (same launches;
-    the weight gradient reads the forward's kept image) and with the kept-image path off, to fp32 rounding with GroupNorm writing the
-    image itself (`GAD_TRAIN_GN_WINO=1`)."""
+    """ResnetBlock2D's training halves as ONE autograd node (ops.GnSiluConv3x3Fn: GroupNorm's launch, then the convolution, whose
+    F(4x4) forward launch keeps its transformed input for the weight gradient) against the two separate nodes: the output and every
+    gradient (input incl. the bypass alias's, norm affine, weight, bias, time-embedding row, residual) bit for bit (same launches),
+    and the weight gradient from the kept image bit for bit the raw launch's on the normalised activation with no kept image."""
     dt = dict(device=dev)
     x0, w0 = nhwc(rnd(B, C, H, W, seed=1)), cl_weight(rnd(Cout, C, 3, 3, seed=2, scale=1 / math.sqrt(9 * C)))
     g0, b0, bias0 = (1 + 0.1 * rnd(C, seed=3)).to(dev), rnd(C, seed=4).to(dev), rnd(Cout, seed=5).to(dev)
@@ -376,22 +368,11 @@ def test_gn_silu_conv3x3_training_node(ops, B, C, Cout, H, W, G, bypass):
         return [y.detach(), *torch.autograd.grad(loss, leaves)]
 
     want = run(False)
-    for a, b_ in zip(run(True), want):                   # default: the norm's own launch, the kept image for the weight gradient
+    for a, b_ in zip(run(True), want):                   # the norm's own launch, the kept image for the weight gradient
         assert torch.equal(a, b_)
-    ops.TRAIN_GN_WINO[0] = True                          # GroupNorm writes the image itself
-    try:
-        got = run(True)
-    finally:
-        ops.TRAIN_GN_WINO[0] = False
-    for a, b_ in zip(got, want):
-        close(a, b_)
-    ops.KEEP_WINO_V[0] = False
-    try:
-        same = run(True)
-    finally:
-        ops.KEEP_WINO_V[0] = True
-    for a, b_ in zip(same, want):
-        assert torch.equal(a, b_)
+    with torch.no_grad():
+        h = ops.group_norm(x0, g0, b0, G, 1e-5, True)
+    assert torch.equal(want[4], ops.conv2d_wgrad_raw(dy, h, w0))      # planner-routed, with no kept image
 
 
 def test_winograd_planner_takes_the_large_launches(ops):
