@@ -104,6 +104,7 @@ class HGemmSegArgs(C.Structure):
 
 
 JL_NORMAL, JL_RADEMACHER = 0, 1
+POOL_MAX, POOL_AVG, POOL_AVG_VALID = 0, 1, 2
 
 GEMM_NO_PATCH, GEMM_TAP_MAJOR_K, GEMM_SCALAR_EPILOGUE, GEMM_GENERAL_LOADERS, GN_TWO_PASS = 1, 2, 4, 8, 1
 GEMM_NO_WINO = 16
@@ -193,6 +194,10 @@ SIGNATURES = {
     "gad_add_noise_bcast": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gad_mse_segments_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "gad_mse_segments": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    # score tail (csrc/scorenet.hip)
+    "gad_pool2d": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "gad_resize_bilinear": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
+    "gad_relu": (C.c_int, [_vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

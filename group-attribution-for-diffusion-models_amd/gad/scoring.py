@@ -6,7 +6,8 @@ fetched from a URL (fid_score.py:28) and are unobtainable offline; the feature e
 therefore a *seeded random-weight* conv stack built from the same HIP operators (the tail is
 ~1 % of a coalition's FLOPs), while the score arithmetic - float64 mean / covariance and the
 Frechet distance - is restated exactly (fid_score.py:104-105 and
-pytorch_fid.calculate_frechet_distance)."""
+pytorch_fid.calculate_frechet_distance).  Where the weight files exist, `default_extractor` /
+`is_extractor` put the real InceptionV3 (gad/inception.py, on the same operators) in its place."""
 from __future__ import annotations
 
 import os
@@ -70,10 +71,32 @@ class ScriptedExtractor(nn.Module):
 
 
 def default_extractor(dims, device, seed=1234):
+    """In order: `GAD_FEATURE_NET_TS` (a TorchScript file, stock torch ops); `GAD_INCEPTION_FID_WEIGHTS=/path.pth`
+    (pytorch-fid's InceptionV3 state dict on the HIP operators, gad/inception.py); `GAD_FEATURE_NET=inception-seeded` (the same
+    architecture with seeded weights: what the true tail costs, not what it scores); else the seeded stand-in."""
     path = os.environ.get("GAD_FEATURE_NET_TS")
     if path and os.path.exists(path):
         return ScriptedExtractor(path, device)
+    weights, kind = os.environ.get("GAD_INCEPTION_FID_WEIGHTS"), os.environ.get("GAD_FEATURE_NET")
+    if weights:
+        from .inception import InceptionV3
+        return InceptionV3.from_file(weights, "fid").to(device)
+    if kind == "inception-seeded":
+        from .inception import InceptionV3
+        return InceptionV3.seeded("fid", seed).to(device)
+    if kind:
+        raise ValueError(f"GAD_FEATURE_NET={kind!r}: the only value is 'inception-seeded'")
     return FeatureNet(dims, seed=seed).to(device)
+
+
+def is_extractor(device):
+    """The classifier behind `is` when `GAD_INCEPTION_IS_WEIGHTS=/path.pth` names torchvision's `inception_v3` state dict
+    (reference inception_score.py); None: `is` comes from the feature extractor's first 1000 dims, as before."""
+    path = os.environ.get("GAD_INCEPTION_IS_WEIGHTS")
+    if not path:
+        return None
+    from .inception import InceptionV3
+    return InceptionV3.from_file(path, "torchvision").to(device)
 
 
 from src.attributions.global_scores.fid_score import (calculate_frechet_distance as frechet_distance,  # noqa: E402,F401
@@ -153,11 +176,21 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
     gen_f = compute_features_torch(net, images01, max(batch_size, 256), device)
     mu, sig = feature_stats_torch(gen_f)
     fid = frechet_distance_torch(mu, sig, mu_r, sig_r)
-    probs = torch.softmax(gen_f[:, :1000].double(), dim=1).cpu().numpy()
+    tag = extractor_tag(net)
+    is_key = ("is_net", os.environ.get("GAD_INCEPTION_IS_WEIGHTS"))
+    if is_key not in _REF_STATS:
+        _REF_STATS[is_key] = is_extractor(device)
+    is_net = _REF_STATS[is_key]
+    if is_net is None:
+        probs = torch.softmax(gen_f[:, :1000].double(), dim=1).cpu().numpy()
+    else:                    # the 1000 logits of torchvision's InceptionV3; the row says that `is` has a source of its own
+        logits = torch.cat([is_net.logits(is_net(images01[s:s + batch_size].to(device))) for s in range(0, len(images01), batch_size)], 0)
+        probs = torch.softmax(logits.double(), dim=1).cpu().numpy()
+        tag = f"{tag};is={extractor_tag(is_net)}"
     is_value = inception_score_from_probs(probs)
     precision, recall = calc_pr(make_manifold(gen_f, nhood_size, 10000, 10000, device), m_ref, 10000, 10000, device)
     return {"fid_value": fid, "is": is_value, "precision": precision, "recall": recall,
-            "feature_extractor": extractor_tag(net)}
+            "feature_extractor": tag}
 
 
 def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_size=256, feature_dims=768, max_ref=2000):

@@ -566,6 +566,31 @@ int64_t gad_mse_segments_workspace_bytes(int32_t R, int32_t rows_per_segment, in
 int gad_mse_segments(const float* pred, const float* eps, float* out, int32_t R, int32_t rows_per_segment, int32_t C,
                      int32_t HW, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Score tail: the kernels between the convolutions of InceptionV3 (csrc/scorenet.hip, gad/inception.py; reference
+ * src/attributions/global_scores/fid_score.py:23-107 and inception_score.py through pytorch-fid's InceptionV3, whose
+ * F.max_pool2d / F.avg_pool2d / F.interpolate / F.relu these replace).  fp32 NHWC, bandwidth-bound, 64-bit element
+ * offsets; a float4 path along channels where C % 4 == 0, the strides are multiples of 4 and the pointers 16-byte
+ * aligned, a scalar path otherwise.  Arguments are checked before any HIP call.
+ *
+ * gad_pool2d: y[b][oh][ow][c] = pool over the k x k window at (oh * stride - pad, ow * stride - pad) of x[b][..][..][c];
+ *   k in {2, 3}, stride in {1, 2}, symmetric pad in {0, 1}, Ho = (H + 2 pad - k) / stride + 1 (floor; Wo alike).
+ *   mode GAD_POOL_MAX: padding never wins; GAD_POOL_AVG: sum / k^2 (torch's avg_pool2d default, padding counted);
+ *   GAD_POOL_AVG_VALID: sum / taps inside the map (count_include_pad=False).  x has pixel stride ldx >= C and y pixel stride
+ *   ldy >= C floats: either may be a channel slice of a wider buffer, only channels [0, C) of a pixel are touched.
+ *   relu_in != 0 pools relu(x).
+ * gad_resize_bilinear: F.interpolate(x, (Ho, Wo), mode="bilinear", align_corners=False) without antialiasing - source
+ *   coordinate (o + 0.5) in / out - 0.5 clamped below at 0, upper neighbour clamped to the last row / column - reading
+ *   NCHW x [B][C][H][W], writing NHWC y [B][Ho][Wo][C] = a * v + b.
+ * gad_relu: x[r][c] = max(x[r][c], 0) in place for r < rows, c < C, row stride ld >= C.
+ * ---------------------------------------------------------------------------- */
+enum gad_pool_mode { GAD_POOL_MAX = 0, GAD_POOL_AVG = 1, GAD_POOL_AVG_VALID = 2 };
+int gad_pool2d(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ldx, int32_t ldy, int32_t Ho,
+               int32_t Wo, int32_t k, int32_t stride, int32_t pad, int32_t mode, int32_t relu_in, void* stream);
+int gad_resize_bilinear(const float* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t Ho, int32_t Wo, float a,
+                        float b, void* stream);
+int gad_relu(float* x, int64_t rows, int32_t C, int32_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
