@@ -16,3 +16,4 @@ __version__ = "0.1.0"
 from .scoring import diversity_against_dataset, fid_against_dataset, global_scores_against_dataset  # noqa: F401,E402
 from .sd import UNet2DConditionModel  # noqa: F401,E402
 from .local import LocalBehaviors, local_model_behaviors  # noqa: F401,E402
+from .influence import InfluenceUnlearner  # noqa: F401,E402

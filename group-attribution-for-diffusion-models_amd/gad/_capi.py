@@ -194,6 +194,10 @@ SIGNATURES = {
     "gad_add_noise_bcast": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gad_mse_segments_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "gad_mse_segments": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    # WoodFisher recursion of influence unlearning (csrc/influence.hip)
+    "gad_wf_dots_workspace_bytes": (_i64, [_i64]),
+    "gad_wf_dots": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "gad_wf_update": (C.c_int, [_vp, _vp, _vp, _f64, _i64, _vp]),
     # score tail (csrc/scorenet.hip)
     "gad_pool2d": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gad_resize_bilinear": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),

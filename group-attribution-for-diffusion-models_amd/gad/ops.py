@@ -1605,6 +1605,19 @@ def ema_update_raw(ema, p, decay: float):
     check(_capi.load().gad_ema_update(ema.data_ptr(), p.data_ptr(), p.numel(), decay, _stream()), "gad_ema_update")
 
 
+def wf_dots_raw(o, k, g, dots):
+    """dots[0] = o.g, dots[1] = k.g (fp64 device pair) over three equally long fp32 vectors; partials in the stream's workspace"""
+    ws = workspace(g.device)
+    check(_capi.load().gad_wf_dots(o.data_ptr(), k.data_ptr(), g.data_ptr(), g.numel(), dots.data_ptr(), ws.data_ptr(), ws.numel(),
+                                   _stream()), "gad_wf_dots")
+    return dots
+
+
+def wf_update_raw(o, k, dots, N: float):
+    """k -= dots[1] / (N + dots[0]) * o;  o -= dots[0] / (N + dots[0]) * o  (both from the old o), in place"""
+    check(_capi.load().gad_wf_update(o.data_ptr(), k.data_ptr(), dots.data_ptr(), float(N), o.numel(), _stream()), "gad_wf_update")
+
+
 # ----------------------------------------------------------------------------------
 # transformer-block operators (UNet2DConditionModel)
 # ----------------------------------------------------------------------------------

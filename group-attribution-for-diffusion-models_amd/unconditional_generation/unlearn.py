@@ -3,7 +3,8 @@ model-behaviour score - global (FID / IS / precision / recall, `--model_behavior
 MSE / NRMSE / SSIM against the full model's image and the diffusion loss, `--model_behavior local`) - and one jsonl row.
 
 Entry point kept from the reference (unconditional_generation/unlearn.py): same flags for the sFT path
-(`--method gd`), same coalition semantics (the by_class quirk of :331 included), same jsonl keys
+(`--method gd` / `ga`) and for influence unlearning (`--method iu`, `--iu_ratio`: :509-546 through
+`gad.InfluenceUnlearner`), same coalition semantics (the by_class quirk of :331 included), same jsonl keys
 (:277,834-837,960-968).  The cycle itself is `gad.coalition.CoalitionEngine`: fused training steps,
 EMA weights, 64-image preview, fused-batch DDIM sampling and the Frechet score on the MI355X.
 """
@@ -87,12 +88,54 @@ def coalition(args, dataset):
     return np.arange(len(dataset)), np.array([], dtype=int)
 
 
+def iu_counts(args, remaining_labels, removed_labels):
+    """(forget_count, retain_count) of get_grad (Wfisher.py:113-120).  `--removal_dist shapley` sets args.by_class = True in the
+    reference (:331-335), so it counts the DISTINCT LABELS a loader shows, not its images.  For every other --removal_dist the
+    reference never sets args.by_class and dies with AttributeError; here those count images (the `else` branch)."""
+    if args.removal_dist == "shapley":
+        return int(torch.unique(removed_labels).numel()), int(torch.unique(remaining_labels).numel())
+    return int(removed_labels.numel()), int(remaining_labels.numel())
+
+
+def influence_unlearn(args, backend, config, dataset, model, ema_model, scheduler, remaining_idx, removed_idx):
+    """Influence unlearning (:509-546): the removed and the remaining set's size-weighted gradient sums, their normalised
+    difference pushed through the WoodFisher inverse-Hessian approximation over a fresh shuffle of the remaining loader, one
+    parameter perturbation and ONE EMA step.  Returns len(remaining loader), the reference's `training_steps` (:392)."""
+    device = args.device
+    n_t = scheduler.config.num_train_timesteps
+    unlearner = backend.InfluenceUnlearner(model, scheduler)
+
+    def loader_of(idx):
+        return backend.DeviceLoader(dataset, idx, config["batch_size"], device)
+
+    def draws(loader):
+        for image, _ in loader:
+            noise = torch.randn_like(image)
+            yield image, noise, backend.antithetic_timesteps(n_t, image.shape[0], device)
+
+    remaining = loader_of(remaining_idx)
+    removed = loader_of(removed_idx) if len(removed_idx) else None          # no loader over nothing: count 0, gradient 0
+    no_labels = torch.empty(0, dtype=torch.long)
+    forget_count, retain_count = iu_counts(args, remaining.labels, removed.labels if removed is not None else no_labels)
+    print("Calculating gradients with removed dataset....")
+    forget_grad = unlearner.gradient_sum(draws(removed) if removed is not None else ())
+    print("Calculating gradients with remaining dataset...")
+    retain_grad = unlearner.gradient_sum(draws(remaining))
+    retain_grad.mul_(forget_count / ((forget_count + retain_count) * retain_count))     # weight normalisation, 1^T w = 1 (:528)
+    forget_grad.div_(forget_count + retain_count)                                       # 1 / N of equation (1) (:531)
+    delta_w = unlearner.woodfisher(draws(remaining), retain_count, forget_grad.sub_(retain_grad))
+    print("Applying perturbation...")
+    unlearner.apply(delta_w, args.iu_ratio)
+    ema_model.step(model.parameters())
+    return len(remaining)
+
+
 def main(args, backend=None):
     if backend is None:
         import gad as backend
-    if args.method not in ("gd", "gd_u", "ga", "ga_u"):
-        raise NotImplementedError(f"method={args.method}: the engine implements the sFT family (gd/ga); "
-                                  "iu / lora / esd are baseline methods outside the hot path")
+    if args.method not in ("gd", "gd_u", "ga", "ga_u", "iu"):
+        raise NotImplementedError(f"method={args.method}: the engine implements the sFT family (gd/ga) and influence unlearning "
+                                  "(iu); esd / lora / retrain / prune_fine_tune are not unlearn.py methods here")
     if hasattr(backend, "set_operand_precision"):      # --mixed_precision fp16|bf16 -> bf16 operands, fp32 everything else
         backend.set_operand_precision(args.mixed_precision)
     device = torch.device(args.device)
@@ -109,25 +152,29 @@ def main(args, backend=None):
     model.to(device)
     ema_model.to(device)
     scheduler = backend.DDPMScheduler(**config["scheduler_config"])
-    okw = dict(config["optimizer_config"]["kwargs"])
-    trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
-                                   weight_decay=okw.get("weight_decay", 0.0),
-                                   adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0,
-                                   loss_sign=-1.0 if args.method.startswith("ga") else 1.0)
-    loader = backend.DeviceLoader(dataset, remaining_idx, config["batch_size"], device)
-    n_t = scheduler.config.num_train_timesteps
-    steps_goal = args.gd_steps if args.method.startswith("gd") else int(config["training_steps"]["ga"] // args.ga_ratio)
+    if args.method == "iu":
+        t0 = time.time()
+        steps_goal = influence_unlearn(args, backend, config, dataset, model, ema_model, scheduler, remaining_idx, removed_idx)
+    else:
+        okw = dict(config["optimizer_config"]["kwargs"])
+        trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
+                                       weight_decay=okw.get("weight_decay", 0.0),
+                                       adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0,
+                                       loss_sign=-1.0 if args.method.startswith("ga") else 1.0)
+        loader = backend.DeviceLoader(dataset, remaining_idx, config["batch_size"], device)
+        n_t = scheduler.config.num_train_timesteps
+        steps_goal = args.gd_steps if args.method.startswith("gd") else int(config["training_steps"]["ga"] // args.ga_ratio)
 
-    t0 = time.time()
-    steps = 0
-    while steps < steps_goal:
-        for image, _ in loader:
-            noise = torch.randn_like(image)
-            ts = backend.antithetic_timesteps(n_t, image.shape[0], device)
-            trainer.step(image, noise, ts)
-            steps += 1
-            if steps == steps_goal:
-                break
+        t0 = time.time()
+        steps = 0
+        while steps < steps_goal:
+            for image, _ in loader:
+                noise = torch.randn_like(image)
+                ts = backend.antithetic_timesteps(n_t, image.shape[0], device)
+                trainer.step(image, noise, ts)
+                steps += 1
+                if steps == steps_goal:
+                    break
     if device.type == "cuda":
         torch.cuda.synchronize(device)
     total_steps_time = time.time() - t0

@@ -567,6 +567,26 @@ int gad_mse_segments(const float* pred, const float* eps, float* out, int32_t R,
                      int32_t HW, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * WoodFisher recursion of influence unlearning (csrc/influence.hip; reference src/unlearn/Wfisher.py:200-205,
+ * Singh & Alistarh eq. 2) over three parameter-sized fp32 vectors.  One iteration for a batch gradient g:
+ *   tmp = o.g   kg = k.g      k -= kg / (N + tmp) * o  (the OLD o)      o -= tmp / (N + tmp) * o
+ * Both calls are asynchronous on `stream`, allocate nothing and can be captured into a hipGraph; the coefficients never
+ * visit the host.  28 B per parameter per iteration (3 + 2 reads, 2 writes).
+ * gad_wf_dots: dots[0] = o.g, dots[1] = k.g.  Every product is formed and accumulated in fp64 (an fp32 x fp32 product is
+ *   exact there, so the only rounding is the fp64 summation).  One sweep, a float4 per lane, grid-stride over at most 2048
+ *   workgroups of 256, scalar tail for n % 4; wave, then LDS, then one fp64 pair per workgroup in ws; a single-workgroup
+ *   pass sums the pairs in index order.  No atomics: bit-reproducible, a function of (o, k, g, n) alone.
+ *   ws_bytes >= gad_wf_dots_workspace_bytes(n) (-1 and gad_last_error() if n <= 0), the function the launch sizes its grid by.
+ * gad_wf_update: every thread forms c_k = dots[1] / (N + dots[0]) and c_o = dots[0] / (N + dots[0]) in fp64, rounds each once
+ *   to fp32, then per element k = fmaf(-c_k, o, k) and o = fmaf(-c_o, o, o), both with the old o.  N + dots[0] == 0 follows
+ *   IEEE arithmetic, as in the reference.
+ * o, k, g 16-byte aligned; dots (two doubles) and ws 8-byte aligned; n > 0.  Arguments are checked before any HIP call.
+ * ---------------------------------------------------------------------------- */
+int64_t gad_wf_dots_workspace_bytes(int64_t n);
+int gad_wf_dots(const float* o, const float* k, const float* g, int64_t n, double* dots, void* ws, int64_t ws_bytes, void* stream);
+int gad_wf_update(float* o, float* k, const double* dots, double N, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Score tail: the kernels between the convolutions of InceptionV3 (csrc/scorenet.hip, gad/inception.py; reference
  * src/attributions/global_scores/fid_score.py:23-107 and inception_score.py through pytorch-fid's InceptionV3, whose
  * F.max_pool2d / F.avg_pool2d / F.interpolate / F.relu these replace).  fp32 NHWC, bandwidth-bound, 64-bit element
