@@ -202,6 +202,11 @@ SIGNATURES = {
     "gad_pool2d": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gad_resize_bilinear": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),
     "gad_relu": (C.c_int, [_vp, _i64, _i32, _i32, _vp]),
+    # precision / recall manifolds on fp16 features (csrc/manifold.hip)
+    "gad_manifold_radii_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "gad_manifold_radii": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
+    "gad_manifold_cover_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
+    "gad_manifold_cover": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

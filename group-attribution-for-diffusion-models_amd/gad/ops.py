@@ -1723,3 +1723,40 @@ def cfg_ddim_step_raw(x, eps_uc, guidance: float, alpha_t: float, alpha_prev: fl
     check(_capi.load().gad_cfg_ddim_step(x.data_ptr(), eps_uc.data_ptr(), out.data_ptr(), x.numel(), guidance, alpha_t,
                                          alpha_prev, clip, _stream()), "gad_cfg_ddim_step")
     return out
+
+
+def _req_half_rows(t, name):
+    if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]):
+        raise _capi.GadError(f"{name}: expected a row-major fp16 device matrix, got {t.dtype} {t.device} strides {tuple(t.stride())}")
+    return t
+
+
+def manifold_radii_raw(features, k):
+    """fp16 [N, D] (row stride >= D) -> fp16 [N]: every row's distance to its k-th nearest other row (gad_manifold_radii)."""
+    f = _req_half_rows(features, "manifold features")
+    lib = _capi.load()
+    N, D = f.shape
+    nbytes = lib.gad_manifold_radii_workspace_bytes(N, D, f.stride(0), k)
+    check(nbytes < 0, "gad_manifold_radii_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=f.device)
+    kth = torch.empty(N, dtype=torch.float16, device=f.device)
+    check(lib.gad_manifold_radii(f.data_ptr(), N, D, f.stride(0), k, kth.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+          "gad_manifold_radii")
+    return kth
+
+
+def manifold_cover_raw(probe, target, kth_target):
+    """fp16 [Np, D], [Nt, D], fp16 radii [Nt] -> uint8 [Np]: the probe lies inside some target's ball (gad_manifold_cover)."""
+    p, t = _req_half_rows(probe, "manifold probes"), _req_half_rows(target, "manifold targets")
+    if p.shape[1] != t.shape[1] or kth_target.shape != (t.shape[0],) or kth_target.dtype != torch.float16 \
+            or not kth_target.is_contiguous() or kth_target.device != t.device:
+        raise _capi.GadError("manifold_cover: probes and targets must share D, radii must be contiguous fp16 [Nt] beside the targets")
+    lib = _capi.load()
+    (Np, D), Nt = p.shape, t.shape[0]
+    nbytes = lib.gad_manifold_cover_workspace_bytes(Np, p.stride(0), Nt, t.stride(0), D)
+    check(nbytes < 0, "gad_manifold_cover_workspace_bytes")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    out = torch.empty(Np, dtype=torch.uint8, device=p.device)
+    check(lib.gad_manifold_cover(p.data_ptr(), Np, p.stride(0), t.data_ptr(), Nt, t.stride(0), D, kth_target.data_ptr(),
+                                 out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "gad_manifold_cover")
+    return out

@@ -99,6 +99,22 @@ def is_extractor(device):
     return InceptionV3.from_file(path, "torchvision").to(device)
 
 
+def pr_extractor(device):
+    """The network behind `precision` / `recall` (reference precision_recall.py: VGG16 fc features): `GAD_VGG16_WEIGHTS=/path.pth`
+    names torchvision's `vgg16` state dict (gad/vgg.py on the HIP operators); `GAD_PR_NET=vgg16-seeded` the same architecture
+    with seeded weights (what the true tail costs, not what it scores); None: P/R come from the feature extractor, as before."""
+    weights, kind = os.environ.get("GAD_VGG16_WEIGHTS"), os.environ.get("GAD_PR_NET")
+    if weights:
+        from .vgg import VGG16
+        return VGG16.from_file(weights).to(device)
+    if kind == "vgg16-seeded":
+        from .vgg import VGG16
+        return VGG16.seeded(1234).to(device)
+    if kind:
+        raise ValueError(f"GAD_PR_NET={kind!r}: the only value is 'vgg16-seeded'")
+    return None
+
+
 from src.attributions.global_scores.fid_score import (calculate_frechet_distance as frechet_distance,  # noqa: E402,F401
                                                       compute_features_stats as feature_stats)
 
@@ -155,10 +171,34 @@ def compute_features_torch(net: FeatureNet, images: torch.Tensor, batch_size: in
     return torch.cat([net(images[s:s + batch_size].to(device)) for s in range(0, len(images), batch_size)], 0)
 
 
+def _pr_net(device):
+    """`pr_extractor`, built once per process and setting; nothing is looked up or stored while neither variable is set"""
+    weights, kind = os.environ.get("GAD_VGG16_WEIGHTS"), os.environ.get("GAD_PR_NET")
+    if not weights and not kind:
+        return None
+    pr_key = ("pr_net", weights, kind)
+    if pr_key not in _REF_STATS:
+        _REF_STATS[pr_key] = pr_extractor(device)
+    return _REF_STATS[pr_key]
+
+
+def _pr_reference(pr_net, net, dataset, device, batch_size, nhood_size):
+    """The reference side with a P/R network, under a key of its own: the extractor's moments and the device manifold of
+    `pr_net`'s fp16 features, both from one copy of the dataset (the extractor's own manifold is not built) -> that key."""
+    from src.attributions.global_scores.precision_recall import make_manifold_device
+    key = ("dev-pr", id(dataset), pr_net.tag, nhood_size)
+    if key not in _REF_STATS:
+        ref = dataset.device_tensor(device).add_(1).div_(2)
+        stats = feature_stats_torch(compute_features_torch(net, ref, max(batch_size, 256), device))
+        _REF_STATS[key] = (stats, make_manifold_device(compute_features_torch(pr_net, ref, max(batch_size, 256), device), nhood_size))
+    return key
+
+
 def global_scores_against_dataset(images01, dataset, device, batch_size=512, feature_dims=2048, nhood_size=3):
     """All four global behaviours unlearn.py writes for the CIFAR family (:807-837): fid_value, is, precision,
     recall - with the seeded stand-in extractor in place of Inception / VGG16 (URL-fetched weights):
-    IS uses the softmax of the first 1000 feature dims as class probabilities, P/R the fp16 features.
+    IS uses the softmax of the first 1000 feature dims as class probabilities, P/R the fp16 features
+    (of the network `pr_extractor` names, where it names one: the row's tag then ends in `;pr=<tag>`).
     Features, float64 moments, the Frechet eigendecompositions and the P/R distance tiles all stay on the
     device; only the four scalars come back to the host."""
     from src.attributions.global_scores.inception_score import inception_score_from_probs
@@ -167,7 +207,10 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
     if net is None:
         net = default_extractor(feature_dims, device)
         _REF_STATS["net"] = net
+    pr_net = _pr_net(device)
     key = ("dev", id(dataset))
+    if pr_net is not None:
+        key = _pr_reference(pr_net, net, dataset, device, batch_size, nhood_size)
     if key not in _REF_STATS:
         ref = dataset.device_tensor(device).add_(1).div_(2)
         ref_f = compute_features_torch(net, ref, max(batch_size, 256), device)
@@ -188,7 +231,13 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
         probs = torch.softmax(logits.double(), dim=1).cpu().numpy()
         tag = f"{tag};is={extractor_tag(is_net)}"
     is_value = inception_score_from_probs(probs)
-    precision, recall = calc_pr(make_manifold(gen_f, nhood_size, 10000, 10000, device), m_ref, 10000, 10000, device)
+    if pr_net is None:
+        precision, recall = calc_pr(make_manifold(gen_f, nhood_size, 10000, 10000, device), m_ref, 10000, 10000, device)
+    else:                    # VGG16 fc features, fp16 on the device; radii and coverage by the fused kernel (csrc/manifold.hip)
+        from src.attributions.global_scores.precision_recall import calc_pr_device, make_manifold_device
+        m_gen = make_manifold_device(compute_features_torch(pr_net, images01, max(batch_size, 256), device), nhood_size)
+        precision, recall = calc_pr_device(m_gen, m_ref)
+        tag = f"{tag};pr={extractor_tag(pr_net)}"
     return {"fid_value": fid, "is": is_value, "precision": precision, "recall": recall,
             "feature_extractor": tag}
 

@@ -42,3 +42,20 @@ def calc_pr(manifold_1, manifold_2, row_batch_size, col_batch_size, device):
             hits.append((d <= target.kth.to(d.device).unsqueeze(0)).any(dim=1))
         return torch.cat(hits).to(torch.float32).mean().item()
     return covered(manifold_1, manifold_2), covered(manifold_2, manifold_1)
+
+
+def make_manifold_device(features, nhood_size=3):
+    """make_manifold on the fused kernel (csrc/manifold.hip): the fp16 features stay on their device and no distance tile is
+    formed; `features` [N, D] with D a multiple of 8."""
+    from gad import ops
+    features = features.to(torch.float16).contiguous()
+    return Manifold(features, ops.manifold_radii_raw(features, nhood_size))
+
+
+def calc_pr_device(manifold_1, manifold_2):
+    """calc_pr on the fused kernel: manifold_1 = generated, manifold_2 = reference -> (precision, recall); only the two means
+    come back to the host."""
+    from gad import ops
+    precision = ops.manifold_cover_raw(manifold_1.features, manifold_2.features, manifold_2.kth).float().mean()
+    recall = ops.manifold_cover_raw(manifold_2.features, manifold_1.features, manifold_1.kth).float().mean()
+    return tuple(torch.stack([precision, recall]).tolist())

@@ -611,6 +611,30 @@ int gad_resize_bilinear(const float* x, float* y, int32_t B, int32_t C, int32_t 
                         float b, void* stream);
 int gad_relu(float* x, int64_t rows, int32_t C, int32_t ld, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Improved precision / recall manifolds on fp16 features (csrc/manifold.hip; reference
+ * src/attributions/global_scores/precision_recall.py compute_kth / calc_pr, Kynkaanniemi et al.) without a distance matrix.
+ * Features are row-major fp16 matrices [rows][D] with a row stride ld >= D in halves; D and every ld are multiples of 8 and
+ * the matrices 16-byte aligned (rows are read as 16-byte chunks; columns [D, ld) are never read).  The distance is defined as
+ *   d2(a, b) = max(0, (|a|^2 + |b|^2) - 2 a.b)   norms and dot product accumulated in fp32 from the exact fp16 values
+ *   d16(a, b) = (half) sqrtf(d2)                  correctly rounded sqrt, round to nearest even
+ * gad_manifold_radii: kth_out[i] (fp16) = the (k+1)-th smallest d16(F_i, F_j) over all j, i included - kthvalue(nhood_size + 1),
+ *   selected on d2 and rounded once.  1 <= k <= 7, N >= k + 1.
+ * gad_manifold_cover: covered_out[i] (0 / 1) = any_j d16(P_i, T_j) <= kth_T[j] (fp16 radii of the targets), compared in the
+ *   fp16-rounded domain.
+ * 128 x 128 tiles of dot products on v_mfma_f32_32x32x16_f16; the target axis is split over workgroups, every split keeps
+ * its 8 smallest d2 (radii) or one flag (cover) per probe row and column half on chip and writes it to the workspace
+ * [2 splits][rows][8 floats | 1 byte] behind the squared norms; a second kernel merges the partials in index order.  No atomics:
+ * bit-reproducible.  Workspace 16-byte aligned, ws_bytes >= the matching *_workspace_bytes(...) (-1 and gad_last_error() if the
+ * arguments are refused), the function the launch sizes itself by.  Arguments are checked before any HIP call.
+ * ---------------------------------------------------------------------------- */
+int64_t gad_manifold_radii_workspace_bytes(int32_t N, int32_t D, int32_t ld, int32_t k);
+int gad_manifold_radii(const void* F, int32_t N, int32_t D, int32_t ld, int32_t k, void* kth_out, void* ws, int64_t ws_bytes,
+                       void* stream);
+int64_t gad_manifold_cover_workspace_bytes(int32_t Np, int32_t ldp, int32_t Nt, int32_t ldt, int32_t D);
+int gad_manifold_cover(const void* P, int32_t Np, int32_t ldp, const void* T, int32_t Nt, int32_t ldt, int32_t D,
+                       const void* kth_T, uint8_t* covered_out, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
