@@ -105,6 +105,7 @@ class HGemmSegArgs(C.Structure):
 
 JL_NORMAL, JL_RADEMACHER = 0, 1
 POOL_MAX, POOL_AVG, POOL_AVG_VALID = 0, 1, 2
+GELU_ERF, GELU_QUICK = 0, 1
 
 GEMM_NO_PATCH, GEMM_TAP_MAJOR_K, GEMM_SCALAR_EPILOGUE, GEMM_GENERAL_LOADERS, GN_TWO_PASS = 1, 2, 4, 8, 1
 GEMM_NO_WINO = 16
@@ -207,6 +208,14 @@ SIGNATURES = {
     "gad_manifold_radii": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
     "gad_manifold_cover_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "gad_manifold_cover": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # Vision Transformer image towers (csrc/vit.hip)
+    "gad_resize_bicubic_patches_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
+    "gad_resize_bicubic_patches": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp, _i64, _vp]),
+    "gad_bicubic_max_taps": (_i32, [_i32, _i32]),
+    "gad_bicubic_taps": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "gad_vit_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
+    "gad_gelu": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp]),
+    "gad_l2_normalize_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp]),
 }
 
 _lib = None

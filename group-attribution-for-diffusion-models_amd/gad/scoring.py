@@ -242,14 +242,53 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
             "feature_extractor": tag}
 
 
+def diversity_extractor(device):
+    """The network behind the CelebA diversity score (reference diversity_score.py:89-120: the BLIP-VQA vision tower's
+    `pooler_output`): `GAD_BLIP_VISION_WEIGHTS=/path` names a state dict of `BlipForQuestionAnswering` or of its `vision_model`
+    (gad/vit.py on the HIP operators); `GAD_DIVERSITY_NET=blip-seeded` the same architecture with seeded weights (what the true
+    tail costs, not what it scores); None: the seeded stand-in, as before."""
+    weights, kind = os.environ.get("GAD_BLIP_VISION_WEIGHTS"), os.environ.get("GAD_DIVERSITY_NET")
+    if weights:
+        from .vit import VisionTower
+        return VisionTower.from_file(weights, "blip_vqa_base").to(device)
+    if kind == "blip-seeded":
+        from .vit import VisionTower
+        return VisionTower.seeded("blip_vqa_base", 1234).to(device)
+    if kind:
+        raise ValueError(f"GAD_DIVERSITY_NET={kind!r}: the only value is 'blip-seeded'")
+    return None
+
+
+def _blip_diversity(weights, kind, images01, dataset, device, num_cluster, batch_size, max_ref):
+    """`diversity_against_dataset` on the BLIP tower: the raw `pooler_output` in fp64, NOT normalised - what
+    diversity_score.py:119-123 clusters."""
+    from src.attributions.global_scores.diversity_score import diversity_from_embeddings
+    key = ("div_net", weights, kind)
+    if key not in _REF_STATS:
+        _REF_STATS[key] = diversity_extractor(device)
+    net = _REF_STATS[key]
+    rkey = ("div_ref", id(dataset), net.tag)
+    if rkey not in _REF_STATS:
+        idx = list(range(min(len(dataset), max_ref)))
+        ref = dataset.device_tensor(device, idx).add(1).div(2).clamp(0, 1)
+        _REF_STATS[rkey] = compute_features_torch(net, ref, batch_size, device).double().cpu().numpy()
+    emb_gen = compute_features_torch(net, images01.to(device), batch_size, device).double().cpu().numpy()
+    entropy, cluster_count, proportions, _, _ = diversity_from_embeddings(_REF_STATS[rkey], emb_gen, num_cluster)
+    return {"entropy": entropy, "cluster_count": cluster_count, "cluster_proportions": proportions,
+            "feature_extractor": extractor_tag(net)}
+
+
 def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_size=256, feature_dims=768, max_ref=2000):
     """The CelebA global behaviour unlearn.py writes (:787-803): entropy / cluster_count / cluster_proportions of
     calculate_diversity_score (diversity_score.py:82-188) - Ward clusters of the reference embeddings, generated samples
     assigned to the nearest cluster mean, log2 entropy of the proportions.  The BLIP-VQA vision tower (hub-fetched, :89-90)
-    is replaced by the seeded stand-in extractor; the reference set ({OUTDIR}/celeba/cluster_imgs there) is the training
+    is replaced by the seeded stand-in extractor unless `diversity_extractor` names the real one; the reference set ({OUTDIR}/celeba/cluster_imgs there) is the training
     set itself (its first `max_ref` items), mapped to [0,1] like the pipeline output.  Embeddings are computed on the
     device; the Ward linkage stays scipy on the host, as in the reference."""
     from src.attributions.global_scores.diversity_score import diversity_from_embeddings
+    weights, kind = os.environ.get("GAD_BLIP_VISION_WEIGHTS"), os.environ.get("GAD_DIVERSITY_NET")
+    if weights or kind:
+        return _blip_diversity(weights, kind, images01, dataset, device, num_cluster, batch_size, max_ref)
     key = ("div_net", feature_dims)
     net = _REF_STATS.get(key)
     if net is None:

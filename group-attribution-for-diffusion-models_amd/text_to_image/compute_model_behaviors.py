@@ -15,6 +15,18 @@ pair), samples stay latents, and the CLIP / aesthetic scorers are a seeded stand
 scores, quantiles, schema - is the reference's).  SSIM and NRMSE (:336-356, scikit-image's `structural_similarity` /
 `normalized_root_mse` on the two uint8 PIL images) are restated here on uint8 pseudo-images of the latents
 (`latents_to_uint8`: the pipeline's own (x/2+0.5).clamp(0,1)*255 round, with latents/4 in the VAE decoder's place).
+
+Where the published files exist the stand-ins give way (nothing changes while none of these is set):
+  GAD_VAE_DECODER_TS=/path/decoder.pt   a TorchScript module mapping latents [B,4,h,w], already divided by the VAE's scaling
+      factor (0.18215) by this caller, to images in [-1, 1]; stock torch ops, off the hand-written path, like
+      GAD_FEATURE_NET_TS.  `ssim` and `nrmse` then run on the decoded uint8 images, and --img_dir stores them too.
+  GAD_CLIP_B32_WEIGHTS, GAD_CLIP_L14_WEIGHTS, GAD_AESTHETIC_WEIGHTS (all three, with a decoder: four-channel latents are not
+      images)   OpenAI CLIP ViT-B/32, open-CLIP ViT-L-14 (openai weights) and LAION's nn.Linear(768, 1) head on the HIP
+      operators (gad/vit.py): `clip_similarity` is the B/32 cosine of the two decoded images, `clip_prompt_score` the B/32
+      cosine against the prompt embedding - the text tower is not part of this project, so it is read from the
+      --prompt_embeds file's key `clip_prompt` ([embed_dim], normalised on load) - and `aesthetic_score` the head on the L/14
+      unit embedding.  `feature_extractor` becomes the `;`-joined tags.
+  GAD_SD_SCORER=clip-seeded   the same architectures with seeded weights: what the true tail costs, not what it scores.
 """
 import argparse
 import json
@@ -126,7 +138,7 @@ def has_duplicate(args) -> bool:
     return df.shape[0] > 0
 
 
-def assemble_row(args, lists: dict, times: dict, remaining_idx, removal_idx) -> dict:
+def assemble_row(args, lists: dict, times: dict, remaining_idx, removal_idx, tag=None) -> dict:
     """The jsonl row of :459-498 from the per-image lists (pure host code; text_to_image/shapley_lds.py reads
     `exp_name`, `remaining_idx` and either `{behaviour}` aggregates or `generated_image_{i}_{behaviour}`)."""
     row = {k: getattr(args, k) for k in REFERENCE_KEYS}
@@ -146,8 +158,79 @@ def assemble_row(args, lists: dict, times: dict, remaining_idx, removal_idx) -> 
     row["clip_prompt_score_time"] = float(np.sum(times["clip_prompt_score"]))
     row["remaining_idx"] = remaining_idx
     row["removal_idx"] = removal_idx
-    row["feature_extractor"] = LatentScorer.TAG        # stand-in scorers: never to be mixed with CLIP / aesthetic-head rows
+    row["feature_extractor"] = tag or LatentScorer.TAG        # stand-in scorers: never to be mixed with CLIP / aesthetic-head rows
     return row
+
+
+VAE_SCALING = 0.18215
+WEIGHT_VARS = ("GAD_CLIP_B32_WEIGHTS", "GAD_CLIP_L14_WEIGHTS", "GAD_AESTHETIC_WEIGHTS")
+
+
+def scorer_settings(prompt_embeds=None):
+    """What the environment asks for, checked before anything is loaded (pure host code) -> None while no CLIP variable is set
+    (the stand-in scorer, whether or not a decoder is), else {"weights": {variable: path} or None for the seeded towers}.
+    `prompt_embeds`: the loaded --prompt_embeds dict or None."""
+    kind = os.environ.get("GAD_SD_SCORER")
+    if kind and kind != "clip-seeded":
+        raise ValueError(f"GAD_SD_SCORER={kind!r}: the only value is 'clip-seeded'")
+    weights = {v: os.environ.get(v) for v in WEIGHT_VARS}
+    if not kind and not any(weights.values()):
+        return None
+    if not kind and not all(weights.values()):
+        raise ValueError("the CLIP scorers need all of " + ", ".join(WEIGHT_VARS) + "; not set: "
+                         + ", ".join(v for v, p in weights.items() if not p))
+    if not os.environ.get("GAD_VAE_DECODER_TS"):
+        raise ValueError("the CLIP image towers score images, and four-channel latents are not images: set GAD_VAE_DECODER_TS "
+                         "to a TorchScript VAE decoder")
+    if prompt_embeds is None or "clip_prompt" not in prompt_embeds:
+        raise ValueError("the CLIP text tower is not part of this project: with the CLIP scorers the --prompt_embeds file must "
+                         "carry the prompt's CLIP ViT-B/32 text embedding under the key 'clip_prompt'")
+    return {"weights": weights if all(weights.values()) else None}
+
+
+class ScriptedDecoder:
+    """`GAD_VAE_DECODER_TS`: latents [1,4,h,w] (as the pipeline returns them) -> the PIL image the reference's pipeline makes
+    of them, as uint8 [H,W,3] on the host and as [1,3,H,W] in [0,1] on the device (the uint8 values / 255: the scorers of the
+    reference see the PIL image)."""
+
+    def __init__(self, path, device):
+        import hashlib
+        self.mod = torch.jit.load(path, map_location=device).eval()
+        with open(path, "rb") as f:
+            self.tag = f"torchscript:{os.path.basename(path)}:{hashlib.sha256(f.read()).hexdigest()[:12]}"
+
+    @torch.no_grad()
+    def __call__(self, lat):
+        x = (self.mod(lat.float() / VAE_SCALING).float() / 2 + 0.5).clamp(0, 1)
+        u8 = (x * 255).round()
+        return u8[0].permute(1, 2, 0).to(torch.uint8).cpu().numpy(), (u8 / 255).contiguous()
+
+
+class ClipScorer:
+    """CLIP ViT-B/32 and open-CLIP ViT-L-14 + aesthetic head on the HIP operators (gad/vit.py, imported only here)."""
+
+    def __init__(self, settings, prompt, device):
+        from gad import vit
+        w = settings["weights"]
+        if w:
+            self.b32 = vit.VisionTower.from_file(w["GAD_CLIP_B32_WEIGHTS"], "clip_vit_b32").to(device)
+            self.l14 = vit.VisionTower.from_file(w["GAD_CLIP_L14_WEIGHTS"], "clip_vit_l14").to(device)
+            self.head = vit.AestheticHead.from_file(self.l14, w["GAD_AESTHETIC_WEIGHTS"]).to(device)
+        else:
+            self.b32 = vit.VisionTower.seeded("clip_vit_b32").to(device)
+            self.l14 = vit.VisionTower.seeded("clip_vit_l14").to(device)
+            self.head = vit.AestheticHead.seeded(self.l14).to(device)
+        prompt = prompt.detach().float().reshape(-1)
+        if prompt.numel() != self.b32.dims:
+            raise ValueError(f"--prompt_embeds: 'clip_prompt' has {prompt.numel()} entries, the image tower embeds into {self.b32.dims}")
+        self.prompt = torch.nn.functional.normalize(prompt, dim=0).to(device)
+        self.tag = ";".join((self.b32.tag, self.l14.tag, self.head.tag))
+
+    def embed(self, image01):
+        return self.b32.embed_unit(image01)[0]
+
+    def aesthetic(self, image01):
+        return self.head(image01)[0].item()
 
 
 class LatentScorer:
@@ -174,6 +257,8 @@ def main(args, backend=None):
         print(f"Found duplicate record in database at {args.db}. Process cancelled.")
         return False
     device = torch.device(args.device)
+    pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False) if args.prompt_embeds else None
+    settings = scorer_settings(pe)                                             # refusals come before anything is loaded
     prompt = PromptConfig.artbench_config[args.cls]                           # :192-194 (kept for the record)
     ucfg = json.loads(args.unet_overrides) if args.unet_overrides else {}
 
@@ -203,7 +288,6 @@ def main(args, backend=None):
 
     ctx_dim = ref_unet.config.cross_attention_dim
     if args.prompt_embeds:
-        pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False)
         cond, uncond = pe["cond"].float(), pe["uncond"].float()
     else:                                                                      # seeded stand-in for CLIP-text(prompt)
         import hashlib
@@ -215,7 +299,8 @@ def main(args, backend=None):
     pipe = backend.StableDiffusionLatentPipeline(unet)
     noise_sched = backend.DDPMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                         num_train_timesteps=1000)
-    scorer = LatentScorer(device)
+    decoder = ScriptedDecoder(os.environ["GAD_VAE_DECODER_TS"], device) if os.environ.get("GAD_VAE_DECODER_TS") else None
+    scorer = LatentScorer(device) if settings is None else ClipScorer(settings, pe["clip_prompt"], device)
     ref_gen = torch.Generator(device=device).manual_seed(args.seed)            # :200-201,216-219
     gen = torch.Generator(device=device).manual_seed(args.seed)
     noise_gen = torch.Generator(device=device).manual_seed(args.seed)
@@ -247,10 +332,15 @@ def main(args, backend=None):
         lat = pipe(cond, uncond, generator=gen, **kw).latents                   # :319-326
         sync()
         t_gen = time.time() - t_gen
+        if decoder is None:
+            ref_u8, u8 = latents_to_uint8(ref_lat), latents_to_uint8(lat)
+            stored = {"reference": ref_lat.cpu(), "sample": lat.cpu()}
+        else:                                                                   # the decoded images, as the reference's PIL pair
+            (ref_u8, ref_img), (u8, img) = decoder(ref_lat), decoder(lat)
+            stored = {"reference": ref_lat.cpu(), "sample": lat.cpu(), "reference_image": torch.from_numpy(ref_u8),
+                      "sample_image": torch.from_numpy(u8)}
         if args.img_dir is not None:
-            torch.save({"reference": ref_lat.cpu(), "sample": lat.cpu()},
-                       os.path.join(args.img_dir, f"latents_seed={args.seed}_sample_{i}.pt"))
-        ref_u8, u8 = latents_to_uint8(ref_lat), latents_to_uint8(lat)
+            torch.save(stored, os.path.join(args.img_dir, f"latents_seed={args.seed}_sample_{i}.pt"))
         t0 = time.time()                                                        # ssim (:336-346)
         lists["ssim"].append(structural_similarity_u8(ref_u8, u8, data_range=255))
         times["ssim"].append(time.time() - t0 + t_gen)
@@ -258,7 +348,7 @@ def main(args, backend=None):
         lists["nrmse"].append(normalized_root_mse_u8(ref_u8, u8))
         times["nrmse"].append(time.time() - t0 + t_gen)
         t0 = time.time()                                                        # clip similarity (:358-378)
-        e_ref, e = scorer.embed(ref_lat), scorer.embed(lat)
+        e_ref, e = (scorer.embed(ref_lat), scorer.embed(lat)) if settings is None else (scorer.embed(ref_img), scorer.embed(img))
         lists["clip_similarity"].append(torch.dot(e_ref, e).item())
         times["clip_similarity"].append(time.time() - t0 + t_gen)
         t0 = time.time()                                                        # clip prompt score (:380-388)
@@ -272,7 +362,7 @@ def main(args, backend=None):
         sync()
         times["simple_loss"].append(time.time() - t0)
         t0 = time.time()                                                        # aesthetic score (:419-431)
-        lists["aesthetic_score"].append(torch.dot(e, scorer.head).item())
+        lists["aesthetic_score"].append(torch.dot(e, scorer.head).item() if settings is None else scorer.aesthetic(img))
         times["aesthetic_score"].append(time.time() - t0 + t_gen)
         done += 1
         if args.ckpt_path is not None and done % args.ckpt_freq == 0:            # :433-457
@@ -283,7 +373,7 @@ def main(args, backend=None):
             torch.save(ck, args.ckpt_path)
             print(f"Checkpoint saved tp {args.ckpt_path}")
 
-    row = assemble_row(args, lists, times, remaining_idx, removal_idx)
+    row = assemble_row(args, lists, times, remaining_idx, removal_idx, tag=None if settings is None else scorer.tag)
     with open(args.db, "a+") as f:
         f.write(json.dumps(row) + "\n")
     print(f"Results saved to the database at {args.db}")

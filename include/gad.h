@@ -635,6 +635,46 @@ int64_t gad_manifold_cover_workspace_bytes(int32_t Np, int32_t ldp, int32_t Nt, 
 int gad_manifold_cover(const void* P, int32_t Np, int32_t ldp, const void* T, int32_t Nt, int32_t ldt, int32_t D,
                        const void* kth_T, uint8_t* covered_out, void* ws, int64_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Score tail: the kernels between the contractions of a pre-LN Vision Transformer image tower (csrc/vit.hip, gad/vit.py:
+ * OpenAI CLIP ViT-B/32, open-CLIP ViT-L/14 and the BLIP-VQA vision tower; reference text_to_image/compute_model_behaviors.py:
+ * 243-262,358-431 and src/attributions/global_scores/diversity_score.py:89-120).  fp32, bandwidth-bound, 64-bit element
+ * offsets, a float4 path where widths, strides and pointers allow it and a scalar path otherwise.  Arguments are checked
+ * before any HIP call.
+ *
+ * gad_resize_bicubic_patches: F.interpolate(x, (rh, rw), mode="bicubic", antialias=True, align_corners=False) of NCHW
+ *   x [B][3][H][W], cropped to the R x R window at (oy, ox) and cut into (R / P)^2 patches of P x P, written as the matrix
+ *   y [B (R/P)^2][P P 3] = a v + b with (ph, pw, c) fastest - the K-contiguous A operand of the patch embedding.  The
+ *   (rh, rw) image is virtual: it is never stored.  CLIP's Resize(n_px) + CenterCrop(n_px) is rh, rw = the shorter side
+ *   scaled to R with the crop centred; BLIP's plain resize is rh = rw = R, oy = ox = 0.  The filter is PIL's: cubic
+ *   (a = -0.5) widened by fs = max(in / out, 1); output index o has centre c = (o + 0.5) in / out and taps
+ *   [max(0, int(c - 2 fs + 0.5)), min(in, int(c + 2 fs + 0.5))) weighted cubic((x - c + 0.5) / fs) / their sum.  PIL's uint8
+ *   rounding between and after the two passes is NOT reproduced.  The two per-axis tap tables are built in fp64 by a
+ *   pre-kernel into ws (4-byte aligned, ws_bytes >= gad_resize_bicubic_patches_workspace_bytes(...), which returns -1 and sets
+ *   gad_last_error() if the geometry is refused: R % P != 0, a crop outside the resized image, a reduction beyond 15 x, or a
+ *   patch tile that does not fit 64 KB of LDS) and each workgroup keeps its patch's rows of them in LDS.
+ * gad_bicubic_max_taps / gad_bicubic_taps: the same tap function on the HOST in fp64 (no HIP call): for resized indices
+ *   [origin, origin + n) of an axis in -> out, start[o], count[o] and w[o][kmax] (zero past count), kmax = gad_bicubic_max_taps.
+ * gad_vit_tokens: out[b][t][:] = LN((t == 0 ? cls : patches[b][t - 1]) + pos[t]) for patches [B][T - 1][C], cls [C],
+ *   pos [T][C], out [B][T][C]; LN is LayerNorm over C with gamma, beta, eps (two-pass statistics), or the identity when
+ *   gamma == beta == NULL.
+ * gad_gelu: in place on x[r][c], r < rows, c < C, row stride ld >= C; GAD_GELU_ERF: x (1 + erf(x / sqrt 2)) / 2,
+ *   GAD_GELU_QUICK: x sigmoid(1.702 x).
+ * gad_l2_normalize_rows: x[r][:] /= |x[r]|_2 in place (row stride ld >= C), fp32 accumulation of a power-of-two scaled row;
+ *   no eps: a zero row becomes NaN.
+ * ---------------------------------------------------------------------------- */
+enum gad_gelu_kind { GAD_GELU_ERF = 0, GAD_GELU_QUICK = 1 };
+int64_t gad_resize_bicubic_patches_workspace_bytes(int32_t H, int32_t W, int32_t rh, int32_t rw, int32_t oy, int32_t ox, int32_t R,
+                                                   int32_t P);
+int gad_resize_bicubic_patches(const float* x, float* y, int32_t B, int32_t H, int32_t W, int32_t rh, int32_t rw, int32_t oy,
+                               int32_t ox, int32_t R, int32_t P, float a, float b, void* ws, int64_t ws_bytes, void* stream);
+int32_t gad_bicubic_max_taps(int32_t in, int32_t out);
+int gad_bicubic_taps(int32_t in, int32_t out, int32_t origin, int32_t n, int32_t* start, int32_t* count, double* w);
+int gad_vit_tokens(const float* patches, const float* cls, const float* pos, const float* gamma, const float* beta, float* out,
+                   int32_t B, int32_t T, int32_t C, float eps, void* stream);
+int gad_gelu(float* x, int64_t rows, int32_t C, int32_t ld, int32_t kind, void* stream);
+int gad_l2_normalize_rows(float* x, int64_t rows, int32_t C, int32_t ld, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
