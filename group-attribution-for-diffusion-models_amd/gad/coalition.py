@@ -221,7 +221,7 @@ class CoalitionEngine:
         self.base_state = base_state
         from . import scoring
         self.feature_net = scoring.default_extractor(feature_dims, self.device)
-        scoring._REF_STATS["net"] = self.feature_net          # one extractor for every score of this process
+        scoring._REF_STATS[scoring.net_key("fid")] = self.feature_net          # one extractor for every score of this process
         self.opt_kwargs = dict(self.config["optimizer_config"]["kwargs"])
         self.adamw = self.config["optimizer_config"]["class_name"] == "AdamW"
 

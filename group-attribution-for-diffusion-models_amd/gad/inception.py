@@ -14,13 +14,13 @@ variant "fid": pytorch-fid's blocks - averages that exclude the padding in Mixed
 Mixed_7c, a 1008-way fc.  variant "torchvision": averages that count the padding, 1000-way fc, transform_input=False."""
 from __future__ import annotations
 
-import hashlib
 import math
 
 import torch
 
-from . import _capi, ops
-from ._capi import A_CONV, A_KC, B_KC, POOL_AVG, POOL_AVG_VALID, POOL_MAX, ConvGeom, check
+from . import ops
+from ._capi import POOL_AVG, POOL_AVG_VALID, POOL_MAX
+from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
 
 BN_EPS = 1e-3
 VARIANTS = {"fid": 1008, "torchvision": 1000}       # variant -> fc outputs
@@ -111,20 +111,19 @@ def seeded_state_dict(variant, seed):
     return sd
 
 
-class InceptionV3:
+class InceptionV3(Extractor):
     """[B,3,H,W] in [0,1] -> pool3 [B,2048] (`forward`); `logits(pool3)` -> [B, 1008 | 1000]."""
 
+    owner = "InceptionV3"
     dims = 2048
     max_batch = 64           # images per pass through the trunk (the 147 x 147 x 64 map of 64 images is 354 MB)
 
     def __init__(self, variant="fid", state_dict=None, tag=None):
         if variant not in VARIANTS:
             raise ValueError(f"InceptionV3 variant {variant!r}: use 'fid' or 'torchvision'")
-        self.variant, self.tag = variant, tag or f"inception-{variant}-unloaded"
+        self.variant = variant
         self.avg = POOL_AVG_VALID if variant == "fid" else POOL_AVG
-        self.w = {}
-        if state_dict is not None:
-            self.load_state_dict(state_dict)
+        super().__init__(tag or f"inception-{variant}-unloaded", state_dict)
 
     @classmethod
     def seeded(cls, variant="fid", seed=1234):
@@ -132,56 +131,27 @@ class InceptionV3:
 
     @classmethod
     def from_file(cls, path, variant):
-        with open(path, "rb") as f:
-            digest = hashlib.sha256(f.read()).hexdigest()[:12]
-        return cls(variant, torch.load(path, map_location="cpu", weights_only=True), tag=f"inception-{variant}:{digest}")
+        return cls(variant, load_checkpoint(path), tag=file_tag(f"inception-{variant}", path, basename=False))
 
     def load_state_dict(self, sd):
-        want = expected_shapes(self.variant)
-        for k in sd:
-            if k not in want and not (k.startswith("AuxLogits.") or k.endswith("num_batches_tracked")):
-                raise KeyError(f"InceptionV3({self.variant}): unexpected key {k!r}")
-        for k, shape in want.items():
-            if k not in sd:
-                raise KeyError(f"InceptionV3({self.variant}): missing key {k!r}")
-            if tuple(sd[k].shape) != shape:
-                raise ValueError(f"InceptionV3({self.variant}): {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
+        check_state_dict(f"InceptionV3({self.variant})", sd, expected_shapes(self.variant),
+                         extra=lambda k: k.startswith("AuxLogits.") or k.endswith("num_batches_tracked"))
         self.w = {name: fold_bn(sd[f"{name}.conv.weight"], *(sd[f"{name}.bn.{k}"] for k in BN_KEYS)) for name in _SPEC}
         self.w["fc"] = (sd["fc.weight"].detach().float().contiguous(), sd["fc.bias"].detach().float().contiguous())
-        return self
-
-    def to(self, device):
-        self.w = {k: (w.to(device), b.to(device)) for k, (w, b) in self.w.items()}
         return self
 
     # ---- launches ----
     def _conv(self, x, name, out=None, c0=0, relu=True):
         """BasicConv2d `name` of x [B,H,W,Cin]; into channels [c0, c0 + Cout) of `out` [B,Ho,Wo,Ctot] if given (no ReLU: the
         block's one pass does it), else into a tensor of its own (ReLU'd unless relu=False)."""
-        ci, co, kh, kw, stride, ph, pw = _SPEC[name]
-        w, b = self.w[name]
-        Bn, H, W, _ = x.shape
-        Ho, Wo = (H + 2 * ph - kh) // stride + 1, (W + 2 * pw - kw) // stride + 1
-        own = out is None
-        if own:
-            out = torch.empty((Bn, Ho, Wo, co), device=x.device, dtype=torch.float32)
-        ld = out.shape[-1]
-        ops.gemm_raw(x, w, out[..., c0:c0 + co], A_CONV, B_KC, Bn * Ho * Wo, co, kh * kw * ci, 0, kh * kw * ci, ld,
-                     geom=ConvGeom(H, W, ci, ci, Ho, Wo, kh, kw, stride, ph, pw, 0), bias=b, force_f32=True)
-        if own and relu:
-            _relu(out)
-        return out
-
-    def _pool(self, x, out, c0, k, stride, pad, mode, relu_in=False):
-        Bn, H, W, Cn = x.shape
-        check(_capi.load().gad_pool2d(x.data_ptr(), out[..., c0:].data_ptr(), Bn, H, W, Cn, Cn, out.shape[-1], out.shape[1],
-                                      out.shape[2], k, stride, pad, mode, int(relu_in), ops._stream()), "gad_pool2d")
-        return out
+        _, _, kh, kw, stride, ph, pw = _SPEC[name]
+        y = ops.conv_krsc_raw(x, *self.w[name], kh, kw, stride, ph, pw, out, c0)
+        return ops.relu_raw(y) if out is None and relu else y
 
     def _maxpool(self, x, relu_in):
         Bn, H, W, Cn = x.shape
         out = torch.empty((Bn, (H - 3) // 2 + 1, (W - 3) // 2 + 1, Cn), device=x.device, dtype=torch.float32)
-        return self._pool(x, out, 0, 3, 2, 0, POOL_MAX, relu_in)
+        return ops.pool2d_raw(x, out, 0, 3, 2, 0, POOL_MAX, relu_in)
 
     def _block(self, x, ctot, stride=1):
         Bn, H, W, _ = x.shape
@@ -189,7 +159,7 @@ class InceptionV3:
         return torch.empty((Bn, Ho, Wo, ctot), device=x.device, dtype=torch.float32)
 
     def _pool_branch(self, x, p, y, c0, mode=None):
-        t = self._pool(x, torch.empty_like(x), 0, 3, 1, 1, self.avg if mode is None else mode)
+        t = ops.pool2d_raw(x, torch.empty_like(x), 0, 3, 1, 1, self.avg if mode is None else mode)
         self._conv(t, f"{p}.branch_pool", y, c0)
 
     def mixed_a(self, x, p):
@@ -200,15 +170,15 @@ class InceptionV3:
         t = self._conv(self._conv(x, f"{p}.branch3x3dbl_1"), f"{p}.branch3x3dbl_2")
         self._conv(t, f"{p}.branch3x3dbl_3", y, 128)
         self._pool_branch(x, p, y, 224)
-        return _relu(y)
+        return ops.relu_raw(y)
 
     def mixed_6a(self, x, p="Mixed_6a"):
         y = self._block(x, 768, 2)
         self._conv(x, f"{p}.branch3x3", y, 0)
         t = self._conv(self._conv(x, f"{p}.branch3x3dbl_1"), f"{p}.branch3x3dbl_2")
         self._conv(t, f"{p}.branch3x3dbl_3", y, 384)
-        self._pool(x, y, 480, 3, 2, 0, POOL_MAX)
-        return _relu(y)
+        ops.pool2d_raw(x, y, 480, 3, 2, 0, POOL_MAX)
+        return ops.relu_raw(y)
 
     def mixed_c(self, x, p):
         y = self._block(x, 768)
@@ -220,7 +190,7 @@ class InceptionV3:
             t = self._conv(t, f"{p}.branch7x7dbl_{i}")
         self._conv(t, f"{p}.branch7x7dbl_5", y, 384)
         self._pool_branch(x, p, y, 576)
-        return _relu(y)
+        return ops.relu_raw(y)
 
     def mixed_7a(self, x, p="Mixed_7a"):
         y = self._block(x, 1280, 2)
@@ -229,8 +199,8 @@ class InceptionV3:
         for i in (2, 3):
             t = self._conv(t, f"{p}.branch7x7x3_{i}")
         self._conv(t, f"{p}.branch7x7x3_4", y, 320)
-        self._pool(x, y, 512, 3, 2, 0, POOL_MAX)
-        return _relu(y)
+        ops.pool2d_raw(x, y, 512, 3, 2, 0, POOL_MAX)
+        return ops.relu_raw(y)
 
     def mixed_e(self, x, p):
         y = self._block(x, 2048)
@@ -243,17 +213,12 @@ class InceptionV3:
         self._conv(t, f"{p}.branch3x3dbl_3b", y, 1472)
         # pytorch-fid's last block pools with a MAX (FIDInceptionE_2), the one before with the padding-excluding average
         self._pool_branch(x, p, y, 1856, POOL_MAX if (self.variant == "fid" and p == "Mixed_7c") else None)
-        return _relu(y)
+        return ops.relu_raw(y)
 
     def preprocess(self, images_nchw01):
         """[B,3,H,W] in [0,1] -> NHWC [B,299,299,3] in [-1,1]: bilinear resize (align_corners=False) and 2x - 1 in one pass;
         a 299 x 299 input passes through the same kernel as an exact copy."""
-        x = ops._req(images_nchw01.float().contiguous(), "inception input")
-        Bn, Cn, H, W = x.shape
-        y = torch.empty((Bn, RESIZE, RESIZE, Cn), device=x.device, dtype=torch.float32)
-        check(_capi.load().gad_resize_bilinear(x.data_ptr(), y.data_ptr(), Bn, Cn, H, W, RESIZE, RESIZE, 2.0, -1.0, ops._stream()),
-              "gad_resize_bilinear")
-        return y
+        return ops.resize_bilinear_raw(ops._req(images_nchw01.float().contiguous(), "inception input"), RESIZE, 2.0, -1.0)
 
     def trunk(self, x):
         """NHWC [B,299,299,3] in [-1,1] -> the Mixed_7c map [B,8,8,2048]"""
@@ -269,30 +234,12 @@ class InceptionV3:
         x = self.mixed_7a(x)
         return self.mixed_e(self.mixed_e(x, "Mixed_7b"), "Mixed_7c")
 
-    @torch.no_grad()
-    def forward(self, images_nchw01):
-        if not self.w:
-            raise _capi.GadError("InceptionV3: no weights loaded")
-        outs = []
-        for s in range(0, len(images_nchw01), self.max_batch):
-            x = self.trunk(self.preprocess(images_nchw01[s:s + self.max_batch]))
-            b, h, w, c = x.shape
-            outs.append(ops.colsum_raw(x.view(b * h * w, c), segments=b) / float(h * w))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-
-    __call__ = forward
+    def _chunk(self, images_nchw01):
+        x = self.trunk(self.preprocess(images_nchw01))
+        b, h, w, c = x.shape
+        return ops.colsum_raw(x.view(b * h * w, c), segments=b) / float(h * w)
 
     @torch.no_grad()
     def logits(self, pool3):
         w, b = self.w["fc"]
-        x = ops._req(pool3.contiguous(), "inception pool3")
-        y = torch.empty((x.shape[0], w.shape[0]), device=x.device, dtype=torch.float32)
-        ops.gemm_raw(x, w, y, A_KC, B_KC, x.shape[0], w.shape[0], 2048, 2048, 2048, w.shape[0], bias=b, force_f32=True)
-        return y
-
-
-def _relu(t):
-    """in place on a contiguous [..., C] tensor"""
-    Cn = t.shape[-1]
-    check(_capi.load().gad_relu(t.data_ptr(), t.numel() // Cn, Cn, Cn, ops._stream()), "gad_relu")
-    return t
+        return ops.linear_fwd_raw(ops._req(pool3.contiguous(), "inception pool3"), w, b, force_f32=True)

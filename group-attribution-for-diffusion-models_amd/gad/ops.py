@@ -773,12 +773,75 @@ def colsum_raw(dy2d: torch.Tensor, segments=1, out=None):
     return out
 
 
-def linear_fwd_raw(x2d, w, bias=None, residual=None, alpha=1.0):
+def linear_fwd_raw(x2d, w, bias=None, residual=None, alpha=1.0, force_f32=False):
     M, K = x2d.shape
     N = w.shape[0]
     y = _out((M, N), x2d.device)
-    gemm_raw(x2d, w, y, A_KC, B_KC, M, N, K, K, K, N, bias=bias, residual=residual, ldr=N, alpha=alpha)
+    gemm_raw(x2d, w, y, A_KC, B_KC, M, N, K, K, K, N, bias=bias, residual=residual, ldr=N, alpha=alpha, force_f32=force_f32)
     return y
+
+
+# ---- eval launches of the score-tail networks (gad/inception.py, gad/vgg.py, gad/vit.py): each the one call site of its symbol
+def conv_krsc_raw(x, w_krsc, bias, kh, kw, stride, pad_h, pad_w, out=None, c0=0):
+    """x [B,H,W,Cin] * weights already laid out [Cout][KH][KW][Cin] -> channels [c0, c0 + Cout) of `out` [B,Ho,Wo,Ctot], or a
+    tensor of its own; exact fp32, direct route (no Winograd operand)."""
+    Bn, H, W, ci = x.shape
+    co = w_krsc.shape[0]
+    Ho, Wo = (H + 2 * pad_h - kh) // stride + 1, (W + 2 * pad_w - kw) // stride + 1
+    if out is None:
+        out = torch.empty((Bn, Ho, Wo, co), device=x.device, dtype=torch.float32)
+    gemm_raw(x, w_krsc, out[..., c0:c0 + co], A_CONV, B_KC, Bn * Ho * Wo, co, kh * kw * ci, 0, kh * kw * ci, out.shape[-1],
+             geom=ConvGeom(H, W, ci, ci, Ho, Wo, kh, kw, stride, pad_h, pad_w, 0), bias=bias, force_f32=True)
+    return out
+
+
+def relu_raw(t):
+    """in place on a contiguous [..., C] tensor"""
+    Cn = t.shape[-1]
+    check(_capi.load().gad_relu(t.data_ptr(), t.numel() // Cn, Cn, Cn, _stream()), "gad_relu")
+    return t
+
+
+def pool2d_raw(x, out, c0, k, stride, pad, mode, relu_in=False):
+    """k x k pool of x [B,H,W,C] into channels [c0, c0 + C) of `out` [B,Ho,Wo,Ctot]; relu_in: of relu(x)"""
+    Bn, H, W, Cn = x.shape
+    check(_capi.load().gad_pool2d(x.data_ptr(), out[..., c0:].data_ptr(), Bn, H, W, Cn, Cn, out.shape[-1], out.shape[1],
+                                  out.shape[2], k, stride, pad, mode, int(relu_in), _stream()), "gad_pool2d")
+    return out
+
+
+def resize_bilinear_raw(x_nchw, R, a, b):
+    """[B,C,H,W] -> NHWC [B,R,R,C] = a * bilinear(x) + b (align_corners=False)"""
+    Bn, Cn, H, W = x_nchw.shape
+    y = torch.empty((Bn, R, R, Cn), device=x_nchw.device, dtype=torch.float32)
+    check(_capi.load().gad_resize_bilinear(x_nchw.data_ptr(), y.data_ptr(), Bn, Cn, H, W, R, R, a, b, _stream()),
+          "gad_resize_bilinear")
+    return y
+
+
+def gelu_raw(h, kind):
+    """in place on a contiguous [rows, C] tensor; kind: _capi.GELU_ERF | GELU_QUICK"""
+    check(_capi.load().gad_gelu(h.data_ptr(), h.shape[0], h.shape[1], h.shape[1], kind, _stream()), "gad_gelu")
+    return h
+
+
+def l2_normalize_rows_raw(x2d):
+    """in place on a contiguous [rows, C] fp32 device tensor"""
+    _req(x2d, "l2_normalize input")
+    check(_capi.load().gad_l2_normalize_rows(x2d.data_ptr(), x2d.shape[0], x2d.shape[1], x2d.shape[1], _stream()),
+          "gad_l2_normalize_rows")
+    return x2d
+
+
+def layernorm_fwd_raw(x, gamma, beta, eps):
+    """over the last axis of a contiguous tensor -> (y, mean [rows], rstd [rows])"""
+    C_ = x.shape[-1]
+    rows = x.numel() // C_
+    y = torch.empty_like(x)
+    stats = torch.empty((2, rows), device=x.device, dtype=torch.float32)
+    check(_capi.load().gad_layernorm_fwd(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(), stats[0].data_ptr(),
+                                         stats[1].data_ptr(), rows, C_, eps, _stream()), "gad_layernorm_fwd")
+    return y, stats[0], stats[1]
 
 
 def linear_dgrad_raw(dy2d, w):
@@ -1624,14 +1687,7 @@ def wf_update_raw(o, k, dots, N: float):
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps):
-        _req(x, "layernorm x")
-        C_ = x.shape[-1]
-        rows = x.numel() // C_
-        y = torch.empty_like(x)
-        mean = torch.empty(rows, device=x.device, dtype=torch.float32)
-        rstd = torch.empty_like(mean)
-        check(_capi.load().gad_layernorm_fwd(x.data_ptr(), y.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
-                                             mean.data_ptr(), rstd.data_ptr(), rows, C_, eps, _stream()), "gad_layernorm_fwd")
+        y, mean, rstd = layernorm_fwd_raw(_req(x, "layernorm x"), gamma, beta, eps)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.beta_ref = beta
         return y

@@ -18,6 +18,10 @@ import torch.nn as nn
 
 from . import nn as gnn
 from . import ops
+from .extractor import file_tag
+from .inception import InceptionV3
+from .vgg import VGG16
+from .vit import VisionTower
 
 
 class FeatureNet(nn.Module):
@@ -58,10 +62,8 @@ class ScriptedExtractor(nn.Module):
 
     def __init__(self, path, device):
         super().__init__()
-        import hashlib
         self.mod = torch.jit.load(path, map_location=device).eval()
-        with open(path, "rb") as f:
-            self.tag = f"torchscript:{os.path.basename(path)}:{hashlib.sha256(f.read()).hexdigest()[:12]}"
+        self.tag = file_tag("torchscript", path)
         with torch.no_grad():
             self.dims = int(self.mod(torch.zeros(1, 3, 32, 32, device=device)).shape[1])
 
@@ -70,49 +72,88 @@ class ScriptedExtractor(nn.Module):
         return self.mod(images_nchw01.float()).float()
 
 
-def default_extractor(dims, device, seed=1234):
-    """In order: `GAD_FEATURE_NET_TS` (a TorchScript file, stock torch ops); `GAD_INCEPTION_FID_WEIGHTS=/path.pth`
-    (pytorch-fid's InceptionV3 state dict on the HIP operators, gad/inception.py); `GAD_FEATURE_NET=inception-seeded` (the same
-    architecture with seeded weights: what the true tail costs, not what it scores); else the seeded stand-in."""
-    path = os.environ.get("GAD_FEATURE_NET_TS")
-    if path and os.path.exists(path):
-        return ScriptedExtractor(path, device)
-    weights, kind = os.environ.get("GAD_INCEPTION_FID_WEIGHTS"), os.environ.get("GAD_FEATURE_NET")
+# Which network runs for a score: role -> (weights variable, switch variable, its one value, builder from a file, builder
+# seeded).  A weights file wins over the switch (the same architecture with seeded weights: what the true tail costs, not what
+# it scores); any other value of the switch is refused; with neither set the role has no network of its own.
+ROLES = {
+    # pytorch-fid's InceptionV3 state dict (reference fid_score.py), gad/inception.py
+    "fid": ("GAD_INCEPTION_FID_WEIGHTS", "GAD_FEATURE_NET", "inception-seeded",
+            lambda path: InceptionV3.from_file(path, "fid"), lambda seed: InceptionV3.seeded("fid", seed)),
+    # torchvision's `inception_v3` state dict (reference inception_score.py); unset: `is` from the feature extractor's first 1000 dims
+    "is": ("GAD_INCEPTION_IS_WEIGHTS", None, None, lambda path: InceptionV3.from_file(path, "torchvision"), None),
+    # torchvision's `vgg16` state dict (reference precision_recall.py: VGG16 fc features), gad/vgg.py; unset: P/R from the feature extractor
+    "pr": ("GAD_VGG16_WEIGHTS", "GAD_PR_NET", "vgg16-seeded", lambda path: VGG16.from_file(path), lambda seed: VGG16.seeded(seed)),
+    # a state dict of `BlipForQuestionAnswering` or of its `vision_model` (reference diversity_score.py:89-120: the BLIP-VQA
+    # vision tower's `pooler_output`), gad/vit.py
+    "diversity": ("GAD_BLIP_VISION_WEIGHTS", "GAD_DIVERSITY_NET", "blip-seeded",
+                  lambda path: VisionTower.from_file(path, "blip_vqa_base"), lambda seed: VisionTower.seeded("blip_vqa_base", seed)),
+}
+
+
+def _settings(role):
+    """the role's environment, read once: (weights file, switch value), for "fid" also `GAD_FEATURE_NET_TS`"""
+    names = ROLES[role][:2] + (("GAD_FEATURE_NET_TS",) if role == "fid" else ())
+    return tuple(os.environ.get(n) if n else None for n in names)
+
+
+def _build(role, device, settings, seed=1234):
+    """`ROLES`' precedence on `settings` -> the network on `device`, or None with nothing set.  `GAD_FEATURE_NET_TS` (a
+    TorchScript file, stock torch ops) wins for "fid"."""
+    _, switch, value, from_file, seeded = ROLES[role]
+    weights, kind, *ts = settings
+    if ts and ts[0] and os.path.exists(ts[0]):
+        return ScriptedExtractor(ts[0], device)
     if weights:
-        from .inception import InceptionV3
-        return InceptionV3.from_file(weights, "fid").to(device)
-    if kind == "inception-seeded":
-        from .inception import InceptionV3
-        return InceptionV3.seeded("fid", seed).to(device)
+        return from_file(weights).to(device)
+    if kind and kind == value:
+        return seeded(seed).to(device)
     if kind:
-        raise ValueError(f"GAD_FEATURE_NET={kind!r}: the only value is 'inception-seeded'")
-    return FeatureNet(dims, seed=seed).to(device)
+        raise ValueError(f"{switch}={kind!r}: the only value is {value!r}")
+    return None
+
+
+_REF_STATS = {}
+
+
+def net_key(role):
+    """where `resolve` keeps the role's network under the environment as it stands"""
+    return ("net", role) + _settings(role)
+
+
+def resolve(role, device, standin=None):
+    """The role's network, built once per process and setting.  With nothing set: `standin()`, kept likewise, or None -
+    and then nothing is looked up or stored."""
+    settings = _settings(role)
+    key = ("net", role) + settings
+    if key not in _REF_STATS:
+        net = _build(role, device, settings)
+        if net is None:
+            if standin is None:
+                return None
+            net = standin()
+        _REF_STATS[key] = net
+    return _REF_STATS[key]
+
+
+def default_extractor(dims, device, seed=1234):
+    """The network behind `fid_value` (role "fid"), built afresh; with nothing set, the seeded stand-in."""
+    net = _build("fid", device, _settings("fid"), seed)
+    return FeatureNet(dims, seed=seed).to(device) if net is None else net
 
 
 def is_extractor(device):
-    """The classifier behind `is` when `GAD_INCEPTION_IS_WEIGHTS=/path.pth` names torchvision's `inception_v3` state dict
-    (reference inception_score.py); None: `is` comes from the feature extractor's first 1000 dims, as before."""
-    path = os.environ.get("GAD_INCEPTION_IS_WEIGHTS")
-    if not path:
-        return None
-    from .inception import InceptionV3
-    return InceptionV3.from_file(path, "torchvision").to(device)
+    """The classifier behind `is` (role "is"); None: `is` comes from the feature extractor's first 1000 dims, as before."""
+    return _build("is", device, _settings("is"))
 
 
 def pr_extractor(device):
-    """The network behind `precision` / `recall` (reference precision_recall.py: VGG16 fc features): `GAD_VGG16_WEIGHTS=/path.pth`
-    names torchvision's `vgg16` state dict (gad/vgg.py on the HIP operators); `GAD_PR_NET=vgg16-seeded` the same architecture
-    with seeded weights (what the true tail costs, not what it scores); None: P/R come from the feature extractor, as before."""
-    weights, kind = os.environ.get("GAD_VGG16_WEIGHTS"), os.environ.get("GAD_PR_NET")
-    if weights:
-        from .vgg import VGG16
-        return VGG16.from_file(weights).to(device)
-    if kind == "vgg16-seeded":
-        from .vgg import VGG16
-        return VGG16.seeded(1234).to(device)
-    if kind:
-        raise ValueError(f"GAD_PR_NET={kind!r}: the only value is 'vgg16-seeded'")
-    return None
+    """The network behind `precision` / `recall` (role "pr"); None: P/R come from the feature extractor, as before."""
+    return _build("pr", device, _settings("pr"))
+
+
+def diversity_extractor(device):
+    """The network behind the CelebA diversity score (role "diversity"); None: the seeded stand-in, as before."""
+    return _build("diversity", device, _settings("diversity"))
 
 
 from src.attributions.global_scores.fid_score import (calculate_frechet_distance as frechet_distance,  # noqa: E402,F401
@@ -148,38 +189,31 @@ def compute_features(net: FeatureNet, images: torch.Tensor, batch_size: int, dev
     return out
 
 
-_REF_STATS = {}
-
-
-def fid_against_dataset(images01, dataset, device, batch_size=512, feature_dims=2048):
-    """calculate_fid (fid_score.py:23-71) with the training set as the reference distribution (its
-    mu/sigma play the role of the precomputed stats.pkl, :42-58; cached per dataset object)."""
-    net = _REF_STATS.get("net")
-    if net is None:
-        net = default_extractor(feature_dims, device)
-        _REF_STATS["net"] = net
-    key = id(dataset)
-    if key not in _REF_STATS:
-        ref = dataset.device_tensor(device).add_(1).div_(2)
-        _REF_STATS[key] = feature_stats(compute_features(net, ref, max(batch_size, 256), device))
-    mu, sigma = feature_stats(compute_features(net, images01, max(batch_size, 256), device))
-    return frechet_distance(mu, sigma, *_REF_STATS[key])
-
-
 def compute_features_torch(net: FeatureNet, images: torch.Tensor, batch_size: int, device) -> torch.Tensor:
     """Like compute_features but the [N, dims] fp32 feature matrix stays in HBM."""
     return torch.cat([net(images[s:s + batch_size].to(device)) for s in range(0, len(images), batch_size)], 0)
 
 
-def _pr_net(device):
-    """`pr_extractor`, built once per process and setting; nothing is looked up or stored while neither variable is set"""
-    weights, kind = os.environ.get("GAD_VGG16_WEIGHTS"), os.environ.get("GAD_PR_NET")
-    if not weights and not kind:
-        return None
-    pr_key = ("pr_net", weights, kind)
-    if pr_key not in _REF_STATS:
-        _REF_STATS[pr_key] = pr_extractor(device)
-    return _REF_STATS[pr_key]
+def _fid_net(feature_dims, device):
+    """role "fid", with the seeded stand-in where nothing is set: one extractor for every score of this process"""
+    return resolve("fid", device, lambda: FeatureNet(feature_dims).to(device))
+
+
+def _reference_features(dataset, device, batch_size, *nets, features=compute_features_torch):
+    """the training set mapped to [0,1] - one copy of it - through each of `nets` -> their feature matrices"""
+    ref = dataset.device_tensor(device).add_(1).div_(2)
+    return [features(net, ref, max(batch_size, 256), device) for net in nets]
+
+
+def fid_against_dataset(images01, dataset, device, batch_size=512, feature_dims=2048):
+    """calculate_fid (fid_score.py:23-71) with the training set as the reference distribution (its
+    mu/sigma play the role of the precomputed stats.pkl, :42-58; cached per dataset object)."""
+    net = _fid_net(feature_dims, device)
+    key = id(dataset)
+    if key not in _REF_STATS:
+        _REF_STATS[key] = feature_stats(*_reference_features(dataset, device, batch_size, net, features=compute_features))
+    mu, sigma = feature_stats(compute_features(net, images01, max(batch_size, 256), device))
+    return frechet_distance(mu, sigma, *_REF_STATS[key])
 
 
 def _pr_reference(pr_net, net, dataset, device, batch_size, nhood_size):
@@ -188,9 +222,8 @@ def _pr_reference(pr_net, net, dataset, device, batch_size, nhood_size):
     from src.attributions.global_scores.precision_recall import make_manifold_device
     key = ("dev-pr", id(dataset), pr_net.tag, nhood_size)
     if key not in _REF_STATS:
-        ref = dataset.device_tensor(device).add_(1).div_(2)
-        stats = feature_stats_torch(compute_features_torch(net, ref, max(batch_size, 256), device))
-        _REF_STATS[key] = (stats, make_manifold_device(compute_features_torch(pr_net, ref, max(batch_size, 256), device), nhood_size))
+        ref_f, ref_pr = _reference_features(dataset, device, batch_size, net, pr_net)
+        _REF_STATS[key] = (feature_stats_torch(ref_f), make_manifold_device(ref_pr, nhood_size))
     return key
 
 
@@ -203,27 +236,20 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
     device; only the four scalars come back to the host."""
     from src.attributions.global_scores.inception_score import inception_score_from_probs
     from src.attributions.global_scores.precision_recall import calc_pr, make_manifold
-    net = _REF_STATS.get("net")
-    if net is None:
-        net = default_extractor(feature_dims, device)
-        _REF_STATS["net"] = net
-    pr_net = _pr_net(device)
+    net = _fid_net(feature_dims, device)
+    pr_net = resolve("pr", device)
     key = ("dev", id(dataset))
     if pr_net is not None:
         key = _pr_reference(pr_net, net, dataset, device, batch_size, nhood_size)
     if key not in _REF_STATS:
-        ref = dataset.device_tensor(device).add_(1).div_(2)
-        ref_f = compute_features_torch(net, ref, max(batch_size, 256), device)
+        (ref_f,) = _reference_features(dataset, device, batch_size, net)
         _REF_STATS[key] = (feature_stats_torch(ref_f), make_manifold(ref_f, nhood_size, 10000, 10000, device))
     (mu_r, sig_r), m_ref = _REF_STATS[key]
     gen_f = compute_features_torch(net, images01, max(batch_size, 256), device)
     mu, sig = feature_stats_torch(gen_f)
     fid = frechet_distance_torch(mu, sig, mu_r, sig_r)
     tag = extractor_tag(net)
-    is_key = ("is_net", os.environ.get("GAD_INCEPTION_IS_WEIGHTS"))
-    if is_key not in _REF_STATS:
-        _REF_STATS[is_key] = is_extractor(device)
-    is_net = _REF_STATS[is_key]
+    is_net = resolve("is", device)
     if is_net is None:
         probs = torch.softmax(gen_f[:, :1000].double(), dim=1).cpu().numpy()
     else:                    # the 1000 logits of torchvision's InceptionV3; the row says that `is` has a source of its own
@@ -242,42 +268,6 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
             "feature_extractor": tag}
 
 
-def diversity_extractor(device):
-    """The network behind the CelebA diversity score (reference diversity_score.py:89-120: the BLIP-VQA vision tower's
-    `pooler_output`): `GAD_BLIP_VISION_WEIGHTS=/path` names a state dict of `BlipForQuestionAnswering` or of its `vision_model`
-    (gad/vit.py on the HIP operators); `GAD_DIVERSITY_NET=blip-seeded` the same architecture with seeded weights (what the true
-    tail costs, not what it scores); None: the seeded stand-in, as before."""
-    weights, kind = os.environ.get("GAD_BLIP_VISION_WEIGHTS"), os.environ.get("GAD_DIVERSITY_NET")
-    if weights:
-        from .vit import VisionTower
-        return VisionTower.from_file(weights, "blip_vqa_base").to(device)
-    if kind == "blip-seeded":
-        from .vit import VisionTower
-        return VisionTower.seeded("blip_vqa_base", 1234).to(device)
-    if kind:
-        raise ValueError(f"GAD_DIVERSITY_NET={kind!r}: the only value is 'blip-seeded'")
-    return None
-
-
-def _blip_diversity(weights, kind, images01, dataset, device, num_cluster, batch_size, max_ref):
-    """`diversity_against_dataset` on the BLIP tower: the raw `pooler_output` in fp64, NOT normalised - what
-    diversity_score.py:119-123 clusters."""
-    from src.attributions.global_scores.diversity_score import diversity_from_embeddings
-    key = ("div_net", weights, kind)
-    if key not in _REF_STATS:
-        _REF_STATS[key] = diversity_extractor(device)
-    net = _REF_STATS[key]
-    rkey = ("div_ref", id(dataset), net.tag)
-    if rkey not in _REF_STATS:
-        idx = list(range(min(len(dataset), max_ref)))
-        ref = dataset.device_tensor(device, idx).add(1).div(2).clamp(0, 1)
-        _REF_STATS[rkey] = compute_features_torch(net, ref, batch_size, device).double().cpu().numpy()
-    emb_gen = compute_features_torch(net, images01.to(device), batch_size, device).double().cpu().numpy()
-    entropy, cluster_count, proportions, _, _ = diversity_from_embeddings(_REF_STATS[rkey], emb_gen, num_cluster)
-    return {"entropy": entropy, "cluster_count": cluster_count, "cluster_proportions": proportions,
-            "feature_extractor": extractor_tag(net)}
-
-
 def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_size=256, feature_dims=768, max_ref=2000):
     """The CelebA global behaviour unlearn.py writes (:787-803): entropy / cluster_count / cluster_proportions of
     calculate_diversity_score (diversity_score.py:82-188) - Ward clusters of the reference embeddings, generated samples
@@ -286,23 +276,16 @@ def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_s
     set itself (its first `max_ref` items), mapped to [0,1] like the pipeline output.  Embeddings are computed on the
     device; the Ward linkage stays scipy on the host, as in the reference."""
     from src.attributions.global_scores.diversity_score import diversity_from_embeddings
-    weights, kind = os.environ.get("GAD_BLIP_VISION_WEIGHTS"), os.environ.get("GAD_DIVERSITY_NET")
-    if weights or kind:
-        return _blip_diversity(weights, kind, images01, dataset, device, num_cluster, batch_size, max_ref)
-    key = ("div_net", feature_dims)
-    net = _REF_STATS.get(key)
-    if net is None:
-        net = FeatureNet(feature_dims, seed=4321).to(device)
-        _REF_STATS[key] = net
-    rkey = ("div_ref", id(dataset))
+    net = resolve("diversity", device, lambda: FeatureNet(feature_dims, seed=4321).to(device))
+    standin = isinstance(net, FeatureNet)
+
+    def embed(images):       # the tower: the raw `pooler_output` in fp64, NOT normalised - what diversity_score.py:119-123 clusters
+        f = compute_features_torch(net, images, batch_size, device).double()
+        return (torch.nn.functional.normalize(f, dim=1) if standin else f).cpu().numpy()
+    rkey = ("div_ref", id(dataset)) if standin else ("div_ref", id(dataset), net.tag)
     if rkey not in _REF_STATS:
         idx = list(range(min(len(dataset), max_ref)))
-        ref = dataset.device_tensor(device, idx).add(1).div(2).clamp(0, 1)
-        f = compute_features_torch(net, ref, batch_size, device)
-        _REF_STATS[rkey] = torch.nn.functional.normalize(f.double(), dim=1).cpu().numpy()
-    emb_ref = _REF_STATS[rkey]
-    f = compute_features_torch(net, images01.to(device), batch_size, device)
-    emb_gen = torch.nn.functional.normalize(f.double(), dim=1).cpu().numpy()
-    entropy, cluster_count, proportions, _, _ = diversity_from_embeddings(emb_ref, emb_gen, num_cluster)
+        _REF_STATS[rkey] = embed(dataset.device_tensor(device, idx).add(1).div(2).clamp(0, 1))
+    entropy, cluster_count, proportions, _, _ = diversity_from_embeddings(_REF_STATS[rkey], embed(images01.to(device)), num_cluster)
     return {"entropy": entropy, "cluster_count": cluster_count, "cluster_proportions": proportions,
             "feature_extractor": extractor_tag(net)}

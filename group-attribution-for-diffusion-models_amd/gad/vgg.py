@@ -5,7 +5,7 @@ one elementwise torch op on the 3-channel input, the mean subtraction in `prepro
 Eval only.  torchvision's `vgg16`: thirteen 3x3 convolutions (pad 1, bias, ReLU) at widths 64, 64, 128, 128, 256 x 3, 512 x 3,
 512 x 3 with a 2x2 stride-2 max pool after the 2nd, 4th, 7th, 10th and 13th, then `classifier.0` 25088 -> 4096 + ReLU and
 `classifier.3` 4096 -> 4096 + ReLU, whose outputs are the features; no dropout, no `classifier.6`.  Every convolution and both
-Linears are one `gad_gemm` launch (the planner picks Winograd or direct as for any 3x3) plus a `gad_relu` pass; the ReLU in
+Linears are one `gad_gemm` launch (the convolutions on the direct route: no Winograd weight is passed) plus a `gad_relu` pass; the ReLU in
 front of a pool is the pool's own (`relu_in`: max commutes with it).  Activations are fp32 NHWC throughout.
 
 State-dict keys are torchvision's (`features.N.weight/bias`, `classifier.0/3.weight/bias`); extra keys (`classifier.6.*`) are
@@ -24,22 +24,13 @@ columns are permuted once at load.  `resolution` 224 ends in a 7 x 7 map (Adapti
 summed at load (fp64) and fc1 contracts over 512.  Other resolutions are refused."""
 from __future__ import annotations
 
-import hashlib
 import math
-import os
 
 import torch
 
 from . import _capi, ops
-from ._capi import A_CONV, A_KC, B_KC, POOL_MAX, ConvGeom, check
-
-
-def _relu(t):
-    """in place on a contiguous [..., C] tensor"""
-    Cn = t.shape[-1]
-    check(_capi.load().gad_relu(t.data_ptr(), t.numel() // Cn, Cn, Cn, ops._stream()), "gad_relu")
-    return t
-
+from ._capi import POOL_MAX
+from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
 
 # torchvision's cfg "D": (index in `features`, Cin, Cout) of every convolution, and the convolutions a max pool follows
 CONVS = [(0, 3, 64), (2, 64, 64), (5, 64, 128), (7, 128, 128), (10, 128, 256), (12, 256, 256), (14, 256, 256),
@@ -84,9 +75,10 @@ def fold_fc1(weight, side):
     raise ValueError(f"VGG16: a final map of {side} x {side} is not supported (7 or 1)")
 
 
-class VGG16:
+class VGG16(Extractor):
     """[B,3,H,W] in [0,1] -> fc2 features [B,4096] (`forward`)."""
 
+    owner = "VGG16"
     dims = FC
 
     def __init__(self, state_dict=None, tag=None, resolution=224):
@@ -95,11 +87,8 @@ class VGG16:
                              "replicas AdaptiveAvgPool2d(7) makes of it folded into fc1)")
         self.resolution, self.side = resolution, RESOLUTIONS[resolution]
         self.max_batch = 16 if resolution == 224 else 1024     # the 224 x 224 x 64 maps of 16 images are 2 x 205 MB
-        self.tag = tag or "vgg16-unloaded"
-        self.w = {}
         self.mean = torch.tensor(MEAN, dtype=torch.float32).view(1, 3, 1, 1)
-        if state_dict is not None:
-            self.load_state_dict(state_dict)
+        super().__init__(tag or "vgg16-unloaded", state_dict)
 
     @classmethod
     def seeded(cls, seed=1234, resolution=224):
@@ -107,17 +96,10 @@ class VGG16:
 
     @classmethod
     def from_file(cls, path, resolution=224):
-        with open(path, "rb") as f:
-            digest = hashlib.sha256(f.read()).hexdigest()[:12]
-        return cls(torch.load(path, map_location="cpu", weights_only=True), tag=f"vgg16:{os.path.basename(path)}:{digest}",
-                   resolution=resolution)
+        return cls(load_checkpoint(path), tag=file_tag("vgg16", path), resolution=resolution)
 
     def load_state_dict(self, sd):
-        for k, shape in expected_shapes().items():
-            if k not in sd:
-                raise KeyError(f"VGG16: missing key {k!r}")
-            if tuple(sd[k].shape) != shape:
-                raise ValueError(f"VGG16: {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
+        check_state_dict("VGG16", sd, expected_shapes())
         self.w = {}
         for idx, ci, _ in CONVS:
             w = sd[f"features.{idx}.weight"].detach()
@@ -129,60 +111,28 @@ class VGG16:
         return self
 
     def to(self, device):
-        self.w = {k: (w.to(device), b.to(device)) for k, (w, b) in self.w.items()}
         self.mean = self.mean.to(device)
-        return self
+        return super().to(device)
 
     # ---- launches ----
-    def _conv(self, x, idx, relu):
-        w, b = self.w[idx]
-        Bn, H, W, ci = x.shape
-        co = w.shape[0]
-        out = torch.empty((Bn, H, W, co), device=x.device, dtype=torch.float32)
-        ops.gemm_raw(x, w, out, A_CONV, B_KC, Bn * H * W, co, 9 * ci, 0, 9 * ci, co,
-                     geom=ConvGeom(H, W, ci, ci, H, W, 3, 3, 1, 1, 1, 0), bias=b, force_f32=True)
-        return _relu(out) if relu else out
-
     def _maxpool_relu(self, x):
         Bn, H, W, Cn = x.shape
         out = torch.empty((Bn, H // 2, W // 2, Cn), device=x.device, dtype=torch.float32)
-        check(_capi.load().gad_pool2d(x.data_ptr(), out.data_ptr(), Bn, H, W, Cn, Cn, Cn, H // 2, W // 2, 2, 2, 0, POOL_MAX, 1,
-                                      ops._stream()), "gad_pool2d")
-        return out
-
-    def _linear(self, x, name):
-        w, b = self.w[name]
-        y = torch.empty((x.shape[0], w.shape[0]), device=x.device, dtype=torch.float32)
-        ops.gemm_raw(x, w, y, A_KC, B_KC, x.shape[0], w.shape[0], w.shape[1], w.shape[1], w.shape[1], w.shape[0], bias=b,
-                     force_f32=True)
-        return _relu(y)
+        return ops.pool2d_raw(x, out, 0, 2, 2, 0, POOL_MAX, relu_in=True)
 
     def preprocess(self, images_nchw01):
         """[B,3,H,W] in [0,1] -> NHWC [B,R,R,3] = resize(x) - mean (the 1 / std scale lives in the first convolution)"""
         x = ops._req((images_nchw01.float() - self.mean).contiguous(), "vgg16 input")
-        Bn, Cn, H, W = x.shape
-        if Cn != 3:
-            raise _capi.GadError(f"VGG16: expected 3 channels, got {Cn}")
-        R = self.resolution
-        y = torch.empty((Bn, R, R, Cn), device=x.device, dtype=torch.float32)
-        check(_capi.load().gad_resize_bilinear(x.data_ptr(), y.data_ptr(), Bn, Cn, H, W, R, R, 1.0, 0.0, ops._stream()),
-              "gad_resize_bilinear")
-        return y
+        if x.shape[1] != 3:
+            raise _capi.GadError(f"VGG16: expected 3 channels, got {x.shape[1]}")
+        return ops.resize_bilinear_raw(x, self.resolution, 1.0, 0.0)
 
-    @torch.no_grad()
-    def forward(self, images_nchw01):
-        if not self.w:
-            raise _capi.GadError("VGG16: no weights loaded")
-        outs = []
-        for s in range(0, len(images_nchw01), self.max_batch):
-            x = self.preprocess(images_nchw01[s:s + self.max_batch])
-            for idx, _, _ in CONVS:
-                pooled = idx in POOL_AFTER
-                x = self._conv(x, idx, relu=not pooled)
-                if pooled:
-                    x = self._maxpool_relu(x)
-            x = x.reshape(x.shape[0], -1)                 # NHWC flatten: (h, w, c), the order fc1's columns were put in
-            outs.append(self._linear(self._linear(x, "fc1"), "fc2"))
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-
-    __call__ = forward
+    def _chunk(self, images_nchw01):
+        x = self.preprocess(images_nchw01)
+        for idx, _, _ in CONVS:
+            x = ops.conv_krsc_raw(x, *self.w[idx], 3, 3, 1, 1, 1)
+            x = self._maxpool_relu(x) if idx in POOL_AFTER else ops.relu_raw(x)
+        x = x.reshape(x.shape[0], -1)                     # NHWC flatten: (h, w, c), the order fc1's columns were put in
+        for name in ("fc1", "fc2"):
+            x = ops.relu_raw(ops.linear_fwd_raw(x, *self.w[name], force_f32=True))
+        return x

@@ -31,16 +31,15 @@ State dicts (missing keys and wrong shapes are refused by name, extra keys ignor
 The layout follows from the configuration: a tower with an `embed_dim` is CLIP's, one without is BLIP's."""
 from __future__ import annotations
 
-import hashlib
 import math
-import os
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
 from . import _capi, ops
-from ._capi import A_KC, B_KC, GELU_ERF, GELU_QUICK, check
+from ._capi import GELU_ERF, GELU_QUICK, check
+from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
 
 CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
 
@@ -235,39 +234,14 @@ def resize_patches_raw(x, R, P, rh, rw, oy, ox, a=1.0, b=0.0):
     return y
 
 
-def l2_normalize_(x2d):
-    """in place on a contiguous [rows, C] fp32 device tensor"""
-    ops._req(x2d, "l2_normalize input")
-    check(_capi.load().gad_l2_normalize_rows(x2d.data_ptr(), x2d.shape[0], x2d.shape[1], x2d.shape[1], ops._stream()),
-          "gad_l2_normalize_rows")
-    return x2d
-
-
-def _sha12(path):
-    with open(path, "rb") as f:
-        return hashlib.sha256(f.read()).hexdigest()[:12]
-
-
-def _load_file(path):
-    """a state dict from a plain checkpoint, or from a TorchScript archive (OpenAI's CLIP `.pt` files are JIT archives)"""
-    try:
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-    except Exception:
-        sd = torch.jit.load(path, map_location="cpu").state_dict()
-    if isinstance(sd, dict) and "state_dict" in sd and isinstance(sd["state_dict"], dict):
-        sd = sd["state_dict"]
-    return sd
-
-
-class VisionTower:
+class VisionTower(Extractor):
     """[B,3,H,W] in [0,1] -> embeddings [B, embed_dim or width] (`forward`); `embed_unit` L2-normalises them."""
 
     def __init__(self, preset_or_config, state_dict=None, tag=None):
         self.cfg, self.name = _config(preset_or_config)
         _check_config(self.cfg)
+        self.owner = f"VisionTower({self.name})"
         self.dims = self.cfg.embed_dim if self.cfg.embed_dim is not None else self.cfg.width
-        self.tag = tag or f"{self.name}-unloaded"
-        self.w = {}
         # Activations alive at once per image, in floats: the patch matrix g g 3 P P, then T rows of the two residual
         # buffers, the normed copy and the attention output (4 W), the qkv projection (3 W) and the MLP hidden (mlp):
         # B/32 50 x 8448 + 150528 = 0.57 M (2.3 MB), L/14 257 x 11264 + 150528 = 3.0 M (12 MB), BLIP 577 x 8448 + 442368 =
@@ -275,8 +249,7 @@ class VisionTower:
         c = self.cfg
         per_image = 4 * (c.tokens * (7 * c.width + c.mlp) + c.image_size * c.image_size * 3)
         self.max_batch = max(1, min(256, 1 << int(math.log2(max(1, (1 << 29) // per_image)))))
-        if state_dict is not None:
-            self.load_state_dict(state_dict)
+        super().__init__(tag or f"{self.name}-unloaded", state_dict)
 
     @classmethod
     def seeded(cls, preset_or_config, seed=1234):
@@ -285,17 +258,13 @@ class VisionTower:
 
     @classmethod
     def from_file(cls, path, preset):
-        return cls(preset, _load_file(path), tag=f"{preset}:{os.path.basename(path)}:{_sha12(path)}")
+        return cls(preset, load_checkpoint(path, torchscript=True), tag=file_tag(preset, path))
 
     def load_state_dict(self, sd):
         cfg, names = self.cfg, _NAMES[self.cfg.layout]
         want = expected_shapes(cfg)
         prefix = names["prefix"] if any(k.startswith(names["prefix"]) for k in sd) and next(iter(want)) not in sd else ""
-        for k, shape in want.items():
-            if prefix + k not in sd:
-                raise KeyError(f"VisionTower({self.name}): missing key {prefix + k!r}")
-            if tuple(sd[prefix + k].shape) != shape:
-                raise ValueError(f"VisionTower({self.name}): {prefix + k!r} has shape {tuple(sd[prefix + k].shape)}, expected {shape}")
+        check_state_dict(self.owner, sd, want, prefix)
 
         def get(k):
             return sd[prefix + k].detach().float().contiguous()
@@ -322,39 +291,9 @@ class VisionTower:
         self.w = w
         return self
 
-    def to(self, device):
-        def mv(v):
-            if isinstance(v, torch.Tensor):
-                return v.to(device)
-            if isinstance(v, tuple):
-                return tuple(mv(t) for t in v)
-            return {k: mv(t) for k, t in v.items()}
-        self.w = {k: mv(v) for k, v in self.w.items()}
-        return self
-
     # ---- launches ----
-    @staticmethod
-    def _linear(x, wb, residual=None):
-        w, b = wb if isinstance(wb, tuple) else (wb, None)
-        M, K = x.shape
-        N = w.shape[0]
-        y = torch.empty((M, N), device=x.device, dtype=torch.float32)
-        ops.gemm_raw(x, w, y, A_KC, B_KC, M, N, K, K, K, N, bias=b, residual=residual, ldr=N if residual is not None else 0,
-                     force_f32=True)
-        return y
-
     def _ln(self, x, gb):
-        rows, Cn = x.shape
-        y = torch.empty_like(x)
-        stats = torch.empty((2, rows), device=x.device, dtype=torch.float32)
-        check(_capi.load().gad_layernorm_fwd(x.data_ptr(), y.data_ptr(), gb[0].data_ptr(), gb[1].data_ptr(), stats[0].data_ptr(),
-                                             stats[1].data_ptr(), rows, Cn, self.cfg.eps, ops._stream()), "gad_layernorm_fwd")
-        return y
-
-    def _act(self, h):
-        kind = GELU_ERF if self.cfg.act == "gelu" else GELU_QUICK
-        check(_capi.load().gad_gelu(h.data_ptr(), h.shape[0], h.shape[1], h.shape[1], kind, ops._stream()), "gad_gelu")
-        return h
+        return ops.layernorm_fwd_raw(x, *gb, self.cfg.eps)[0]
 
     def tokens(self, images_nchw01):
         """[B,3,H,W] in [0,1] -> the token sequence [B T, W] in front of the first block"""
@@ -362,7 +301,7 @@ class VisionTower:
         x = ops._req(images_nchw01.float().contiguous(), f"{self.name} input")
         Bn, _, H, W = x.shape
         patches = resize_patches_raw(x, cfg.image_size, cfg.patch, *resize_geometry(H, W, cfg.image_size, cfg.layout))
-        emb = self._linear(patches, self.w["patch"])
+        emb = ops.linear_fwd_raw(patches, *self.w["patch"], force_f32=True)
         out = torch.empty((Bn * cfg.tokens, cfg.width), device=x.device, dtype=torch.float32)
         g, b = self.w["ln_pre"] if cfg.ln_pre else (None, None)
         check(_capi.load().gad_vit_tokens(emb.data_ptr(), self.w["cls"].data_ptr(), self.w["pos"].data_ptr(), ops._ptr(g), ops._ptr(b),
@@ -371,44 +310,28 @@ class VisionTower:
 
     def _block(self, x, Bn, blk):
         cfg = self.cfg
-        qkv = self._linear(self._ln(x, blk["ln1"]), blk["qkv"])
+        qkv = ops.linear_fwd_raw(self._ln(x, blk["ln1"]), *blk["qkv"], force_f32=True)
         o = ops.attention_core_qkv_raw(qkv, Bn, cfg.tokens, cfg.width, cfg.heads)
-        x = self._linear(o.view(Bn * cfg.tokens, cfg.width), blk["out"], residual=x)
-        h = self._act(self._linear(self._ln(x, blk["ln2"]), blk["fc"]))
-        return self._linear(h, blk["proj"], residual=x)
+        x = ops.linear_fwd_raw(o.view(Bn * cfg.tokens, cfg.width), *blk["out"], residual=x, force_f32=True)
+        h = ops.linear_fwd_raw(self._ln(x, blk["ln2"]), *blk["fc"], force_f32=True)
+        h = ops.gelu_raw(h, GELU_ERF if cfg.act == "gelu" else GELU_QUICK)
+        return ops.linear_fwd_raw(h, *blk["proj"], residual=x, force_f32=True)
 
-    @torch.no_grad()
+    def _chunk(self, images_nchw01):
+        cfg, Bn = self.cfg, images_nchw01.shape[0]
+        x = self.tokens(images_nchw01)
+        for i in range(cfg.layers):
+            x = self._block(x, Bn, self.w[i])
+        pooled = self._ln(x.view(Bn, cfg.tokens, cfg.width)[:, 0].contiguous(), self.w["ln_post"])
+        return ops.linear_fwd_raw(pooled, self.w["head"], force_f32=True) if cfg.embed_dim is not None else pooled
+
     def forward(self, images_nchw01):
-        if not self.w:
-            raise _capi.GadError(f"VisionTower({self.name}): no weights loaded")
-        cfg, outs = self.cfg, []
         with ops.operand_precision("f32"):                # the attention kernel follows the process-wide switch; this tower is fp32
-            for s in range(0, len(images_nchw01), self.max_batch):
-                chunk = images_nchw01[s:s + self.max_batch]
-                Bn = chunk.shape[0]
-                x = self.tokens(chunk)
-                for i in range(cfg.layers):
-                    x = self._block(x, Bn, self.w[i])
-                pooled = self._ln(x.view(Bn, cfg.tokens, cfg.width)[:, 0].contiguous(), self.w["ln_post"])
-                outs.append(self._linear(pooled, self.w["head"]) if cfg.embed_dim is not None else pooled)
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-
-    __call__ = forward
+            return super().forward(images_nchw01)
 
     def embed_unit(self, images_nchw01):
         out = self.forward(images_nchw01)
-        return l2_normalize_(out if out.is_contiguous() else out.contiguous())
-
-
-def preset_tower(preset, weights_env, seeded, device, seed=1234):
-    """The tower behind an environment variable: `weights_env` names a checkpoint -> `from_file`; else `seeded` -> the seeded
-    architecture (what the true tail costs, not what it scores)."""
-    path = os.environ.get(weights_env)
-    if path:
-        return VisionTower.from_file(path, preset).to(device)
-    if seeded:
-        return VisionTower.seeded(preset, seed).to(device)
-    return None
+        return ops.l2_normalize_rows_raw(out if out.is_contiguous() else out.contiguous())
 
 
 class AestheticHead:
@@ -429,14 +352,10 @@ class AestheticHead:
 
     @classmethod
     def from_file(cls, tower, path):
-        return cls(tower, _load_file(path), tag=f"aesthetic:{os.path.basename(path)}:{_sha12(path)}")
+        return cls(tower, load_checkpoint(path, torchscript=True), tag=file_tag("aesthetic", path))
 
     def load_state_dict(self, sd):
-        for k, shape in (("weight", (1, self.tower.dims)), ("bias", (1,))):
-            if k not in sd:
-                raise KeyError(f"AestheticHead: missing key {k!r}")
-            if tuple(sd[k].shape) != shape:
-                raise ValueError(f"AestheticHead: {k!r} has shape {tuple(sd[k].shape)}, expected {shape}")
+        check_state_dict("AestheticHead", sd, {"weight": (1, self.tower.dims), "bias": (1,)})
         self.weight, self.bias = sd["weight"].detach().float().contiguous(), sd["bias"].detach().float().contiguous()
         return self
 
@@ -447,7 +366,7 @@ class AestheticHead:
     @torch.no_grad()
     def score_unit(self, unit):
         """[B, E] unit embeddings -> [B] scores (one contraction with the bias in its epilogue)"""
-        return VisionTower._linear(unit, (self.weight, self.bias)).view(-1)
+        return ops.linear_fwd_raw(unit, self.weight, self.bias, force_f32=True).view(-1)
 
     def __call__(self, images_nchw01):
         return self.score_unit(self.tower.embed_unit(images_nchw01))

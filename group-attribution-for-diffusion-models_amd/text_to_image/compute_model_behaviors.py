@@ -194,10 +194,9 @@ class ScriptedDecoder:
     reference see the PIL image)."""
 
     def __init__(self, path, device):
-        import hashlib
+        from gad.extractor import file_tag
         self.mod = torch.jit.load(path, map_location=device).eval()
-        with open(path, "rb") as f:
-            self.tag = f"torchscript:{os.path.basename(path)}:{hashlib.sha256(f.read()).hexdigest()[:12]}"
+        self.tag = file_tag("torchscript", path)
 
     @torch.no_grad()
     def __call__(self, lat):

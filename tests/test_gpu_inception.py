@@ -203,7 +203,7 @@ def test_scoring_switch_and_unchanged_default(monkeypatch):
         assert row["feature_extractor"] == "inception-fid-seeded1234"
         assert all(np.isfinite(row[k]) for k in ("fid_value", "is", "precision", "recall"))
         assert row["fid_value"] > 0 and row["is"] > 0.999 and 0 <= row["precision"] <= 1 and 0 <= row["recall"] <= 1
-        assert isinstance(scoring._REF_STATS["net"], inception.InceptionV3)
+        assert isinstance(scoring._REF_STATS[("net", "fid", None, "inception-seeded", None)], inception.InceptionV3)
 
         scoring._REF_STATS.clear()
         monkeypatch.delenv("GAD_FEATURE_NET")

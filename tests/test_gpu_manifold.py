@@ -288,7 +288,7 @@ def test_scoring_switch_writes_the_pr_tag(monkeypatch):
         scoring._REF_STATS.clear()
         row = scoring.global_scores_against_dataset(gen, ds, dev, 64, 256)
         assert row["feature_extractor"] == "standin-seed1234-d256;pr=vgg16-seeded1234"
-        net = scoring._REF_STATS[("pr_net", None, "vgg16-seeded")]
+        net = scoring._REF_STATS[("net", "pr", None, "vgg16-seeded")]
         assert isinstance(net, vgg.VGG16) and net.resolution == 224
         ref_f = scoring.compute_features_torch(net, ds.device_tensor(dev).add_(1).div_(2), 256, dev).half().cpu()
         gen_f = scoring.compute_features_torch(net, gen, 256, dev).half().cpu()

@@ -79,7 +79,7 @@ def test_global_scores_against_dataset_equals_the_host_route():
     ds = create_dataset("toy2", train=True)
     net = scoring.FeatureNet(256).to(dev)
     scoring._REF_STATS.clear()
-    scoring._REF_STATS["net"] = net
+    scoring._REF_STATS[scoring.net_key("fid")] = net
     g = torch.Generator().manual_seed(0)
     gen = (ds.device_tensor("cpu")[:96].add(1).div(2) * 0.8 + 0.1 * torch.rand(96, 3, 32, 32, generator=g)).clamp(0, 1)
     got = scoring.global_scores_against_dataset(gen.to(dev), ds, dev, 64, 256)
@@ -107,7 +107,7 @@ def test_device_diversity_matches_scipy_recomputation():
     g = torch.Generator().manual_seed(1)
     gen = (ds.device_tensor("cpu")[:80].add(1).div(2) + 0.05 * torch.randn(80, 3, 32, 32, generator=g)).clamp(0, 1)
     got = scoring.diversity_against_dataset(gen.to(dev), ds, dev, num_cluster=5, feature_dims=64)
-    net = scoring._REF_STATS[("div_net", 64)]
+    net = scoring._REF_STATS[scoring.net_key("diversity")]
     idx = list(range(min(len(ds), 2000)))
     e_ref = torch.nn.functional.normalize(scoring.compute_features_torch(net, ds.device_tensor(dev, idx).add(1).div(2).clamp(0, 1), 256, dev).double(), dim=1).cpu().numpy()
     e_gen = torch.nn.functional.normalize(scoring.compute_features_torch(net, gen.to(dev), 256, dev).double(), dim=1).cpu().numpy()

@@ -18,7 +18,7 @@ for p in (os.path.join(ROOT, "group-attribution-for-diffusion-models_amd"), ROOT
 import torch  # noqa: E402
 
 import inception_ref as R  # noqa: E402
-from gad import inception  # noqa: E402
+from gad import inception, ops  # noqa: E402
 
 dev = torch.device("cuda:0")
 
@@ -64,24 +64,27 @@ def profile_hip(net, x):
     """-> ({family: ms}, {layer: ms of its convolution launch}, multiply-adds of the convolutions) of one forward; ReLU passes
     are their own family"""
     fam, layer = Events(), Events()
-    saved = (net._conv, net._pool, inception._relu, net.preprocess, inception.ops.colsum_raw, inception.ops.gemm_raw)
+    saved = {n: getattr(ops, n) for n in ("conv_krsc_raw", "gemm_raw", "pool2d_raw", "relu_raw", "resize_bilinear_raw", "colsum_raw")}
+    by_weight = {net.w[name][0].data_ptr(): name for name in inception._SPEC}
     conv_name, macs = [None], [0]
 
     def counted(*a, **kw):
         macs[0] += a[5] * a[6] * a[7]                     # M N K
-        return saved[5](*a, **kw)
+        return saved["gemm_raw"](*a, **kw)
 
-    def conv(x_, name, *a, **kw):
-        conv_name[0] = name
-        return saved[0](x_, name, *a, **kw)
-    gemm = fam.wrap(layer.wrap(counted, lambda *a, **kw: conv_name[0]), lambda *a, **kw: conv_family(conv_name[0]))
-    net._conv, net._pool = conv, fam.wrap(saved[1], "pool2d")
-    inception._relu, net.preprocess = fam.wrap(saved[2], "relu"), fam.wrap(saved[3], "resize + 2x-1")
-    inception.ops.colsum_raw, inception.ops.gemm_raw = fam.wrap(saved[4], "global average"), gemm
+    def conv(x_, w, *a, **kw):
+        conv_name[0] = by_weight[w.data_ptr()]
+        return saved["conv_krsc_raw"](x_, w, *a, **kw)
+    ops.conv_krsc_raw = conv
+    ops.gemm_raw = fam.wrap(layer.wrap(counted, lambda *a, **kw: conv_name[0]), lambda *a, **kw: conv_family(conv_name[0]))
+    for n, family in (("pool2d_raw", "pool2d"), ("relu_raw", "relu"), ("resize_bilinear_raw", "resize + 2x-1"),
+                      ("colsum_raw", "global average")):
+        setattr(ops, n, fam.wrap(saved[n], family))
     try:
         net(x)
     finally:
-        net._conv, net._pool, inception._relu, net.preprocess, inception.ops.colsum_raw, inception.ops.gemm_raw = saved
+        for n, fn in saved.items():
+            setattr(ops, n, fn)
     return fam.totals(), layer.totals(), macs[0]
 
 
