@@ -17,3 +17,4 @@ from .scoring import diversity_against_dataset, fid_against_dataset, global_scor
 from .sd import UNet2DConditionModel  # noqa: F401,E402
 from .local import LocalBehaviors, local_model_behaviors  # noqa: F401,E402
 from .influence import InfluenceUnlearner  # noqa: F401,E402
+from .similarity import cosine_rows, group_aggregate, write_baselines  # noqa: F401,E402

@@ -106,6 +106,7 @@ class HGemmSegArgs(C.Structure):
 JL_NORMAL, JL_RADEMACHER = 0, 1
 POOL_MAX, POOL_AVG, POOL_AVG_VALID = 0, 1, 2
 GELU_ERF, GELU_QUICK = 0, 1
+SIM_X_F32, SIM_X_U8 = 0, 1
 
 GEMM_NO_PATCH, GEMM_TAP_MAJOR_K, GEMM_SCALAR_EPILOGUE, GEMM_GENERAL_LOADERS, GN_TWO_PASS = 1, 2, 4, 8, 1
 GEMM_NO_WINO = 16
@@ -216,6 +217,9 @@ SIGNATURES = {
     "gad_vit_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "gad_gelu": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp]),
     "gad_l2_normalize_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp]),
+    # similarity baselines (csrc/similarity.hip)
+    "gad_cosine_rows_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32]),
+    "gad_cosine_rows": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -675,6 +675,30 @@ int gad_vit_tokens(const float* patches, const float* cls, const float* pos, con
 int gad_gelu(float* x, int64_t rows, int32_t C, int32_t ld, int32_t kind, void* stream);
 int gad_l2_normalize_rows(float* x, int64_t rows, int32_t C, int32_t ld, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * Similarity baselines: every cosine between training rows and generated rows in one pass (csrc/similarity.hip; reference
+ * text_to_image/pixel_similarity.py, clip_similarity.py, baselines.py: x /= x.norm(); q /= q.norm(); x @ q).
+ *   sim[n][m] = (x_n . q_m) / (|x_n| |q_m|)      X [N][D] training rows, Q [M][D] generated rows (fp32), sim [N][M] fp32, dense
+ * x_kind = GAD_SIM_X_F32: X is fp32, ldx in elements, D and ldx multiples of 4; lut is not looked at.
+ * x_kind = GAD_SIM_X_U8:  X is uint8, ldx in bytes, D and ldx multiples of 16; the value of byte u is lut[u], a device table of
+ *   256 floats the caller fills on the host with ((float)u / 255.0f - 0.5f) / 0.5f (ToTensor + Normalize([0.5], [0.5])).
+ * ldq in elements, a multiple of 4; ldx, ldq >= D; X and Q 16-byte aligned; columns [D, ld) are never read.  Any M >= 1: the
+ * columns go in blocks of 64 per pass over X, further blocks read X again.
+ * The contraction runs on v_mfma_f32_32x32x2_f32 from the exact fp32 values (no bf16 / fp16 rounding); |x_n|^2 is accumulated
+ * from the same staged data in the same pass, |q_m|^2 by the first row tile's workgroups alone.  D is split over workgroups
+ * in 64-wide steps: every split writes partial dots [splits][N][M] and partial squared norms [splits][N], [splits][M] to the
+ * workspace and a second kernel adds them in split order and forms dot / (sqrtf(nx) sqrtf(nq)).  No atomics: bit-reproducible,
+ * and at equal `splits` the uint8 path equals the fp32 path on the decoded matrix bit for bit.  splits = 0 lets the launch
+ * choose (from N and D alone), a positive value (<= 4096) forces that many; trailing splits may be ragged or empty.  Rows past
+ * N, columns past M and k past D are zeros, never read from the matrices.  No eps: a zero row gives NaN.  Workspace 16-byte
+ * aligned, ws_bytes >= gad_cosine_rows_workspace_bytes(...) (-1 and gad_last_error() if the arguments are refused), the
+ * function the launch sizes itself by.  Arguments are checked before any HIP call.
+ * ---------------------------------------------------------------------------- */
+enum gad_sim_x_kind { GAD_SIM_X_F32 = 0, GAD_SIM_X_U8 = 1 };
+int64_t gad_cosine_rows_workspace_bytes(int64_t N, int64_t M, int64_t D, int32_t x_kind, int32_t splits);
+int gad_cosine_rows(const void* X, int32_t x_kind, int64_t ldx, const float* lut, const float* Q, int64_t ldq, float* sim,
+                    int64_t N, int64_t M, int64_t D, int32_t splits, void* ws, int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
