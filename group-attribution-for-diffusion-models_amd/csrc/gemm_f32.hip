@@ -2343,6 +2343,8 @@ static int pick_vec(const gad_gemm_args* a) {
   if (bmode == GAD_B_KC && (a->K % 4 != 0 || a->ldb % 4 != 0)) vec = 1;
   if (bmode == GAD_B_MC && (a->N % 4 != 0 || a->ldb % 4 != 0)) vec = 1;
   if ((am == GAD_A_CONV || am == GAD_A_CONVT || bmode == GAD_B_CONV) && (a->g.C % 4 != 0 || a->g.ldx % 4 != 0)) vec = 1;
+  // batched launches: slab z starts at A + z0 * strideA0 + z1 * strideA1 (B likewise), which must stay on the float4 grid too
+  if (a->batch > 1 && (a->strideA0 % 4 != 0 || a->strideA1 % 4 != 0 || a->strideB0 % 4 != 0 || a->strideB1 % 4 != 0)) vec = 1;
   return vec;
 }
 

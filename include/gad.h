@@ -69,6 +69,9 @@ typedef struct gad_gemm_args {
   int32_t lda, ldb, ldc;
   /* batch z = z0 * batch_inner + z1 ; pointer offset = z0*stride?0 + z1*stride?1 (floats) */
   int32_t batch, batch_inner;
+  /* With batch > 1 the strides are part of the float4 decision (gad_gemm_plan's vec): an A or B stride that is not a
+   * multiple of 4 floats puts the launch on the dword loaders (vec 1, fp32 products whatever operand_precision says), a C
+   * stride that is not one puts it on the scalar epilogue.  With batch <= 1 they are ignored. */
   int64_t strideA0, strideA1, strideB0, strideB1, strideC0, strideC1;
   gad_conv_geom g;          /* used by the CONV / CONVT / WDGRAD / B_CONV modes              */
   /* epilogue: C = alpha*acc + bias[n] + rowadd[m / rows_per_group][n] + residual[m][n]      */

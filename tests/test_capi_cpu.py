@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from gad import _capi
 
 
@@ -342,6 +344,33 @@ def test_gemm_route_table_matches_the_recorded_one(golden_dir):
     assert (((kid == 0) | (kid == 1)) & (ws > 0)).any()                                                # generic split-K
     assert ((kid == 2) & fwd & (ws > 0)).any() and ((kid == 2) & wgrad & (ws > 0)).any()               # patch split-K, patch wgrad
     assert ((kid == 6) & (ws > 0)).any()                                                               # three-launch F(4x4)
+
+
+@pytest.mark.parametrize("pair", [(F.A_KC, F.B_KC), (F.A_KC, F.B_MC), (F.A_MC, F.B_MC)])
+def test_batch_strides_are_part_of_the_float4_decision(pair):
+    """A batched launch whose A or B slabs do not start on the float4 grid takes the dword loaders and, whatever
+    operand_precision allows, multiplies in fp32 (gad.h, next to strideA0): one odd stride out of the four is enough.  With
+    batch <= 1 the strides are not read."""
+    lib = _capi.load()
+    tile, sk, vec = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+
+    def query(batch, **strides):
+        a = _route_args(*pair, 64, 64, 64, batch=batch)
+        a.batch_inner, a.operand_precision = 3, 1
+        a.strideA0, a.strideA1, a.strideB0, a.strideB1 = 64 * 64 * 3, 64 * 64, 64 * 64 * 3, 64 * 64
+        a.strideC0, a.strideC1 = 64 * 64 * 3, 64 * 64
+        for k, v in strides.items():
+            setattr(a, k, v)
+        assert lib.gad_gemm_plan(ctypes.byref(a), ctypes.byref(tile), ctypes.byref(sk), ctypes.byref(vec)) == 0
+        return vec.value, lib.gad_gemm_uses_bf16(ctypes.byref(a)), lib.gad_gemm_kernel_id(ctypes.byref(a))
+
+    assert query(6) == (4, 1, 1)
+    for field in ("strideA0", "strideA1", "strideB0", "strideB1"):
+        for odd in (9, 64 * 64 + 1, 64 * 64 + 2, 64 * 64 * 3 - 1):
+            assert odd % 4 != 0
+            assert query(6, **{field: odd}) == (1, 0, 0), (field, odd)
+            assert query(1, **{field: odd})[0] == 4, (field, odd)
+            assert query(6, **{field: odd + 4 - odd % 4}) == (4, 1, 1), (field, odd)
 
 
 def test_winograd_stage_flags_are_refused_off_their_route():

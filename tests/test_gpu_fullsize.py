@@ -34,10 +34,26 @@ def _conv_case(Cin, Cout, B=512, H=32):  # noqa: E302
                                          (672, 672, 32, 16), (224, 448, 32, 32), (192, 192, 1024, 4)])
 def test_conv_fwd_full_size_properties(ops, Cin, Cout, B, H):
     """B=512 (16 fused reference batches) x 32x32: the dominant launch of the sampler (and the 16x16 level at the
-    training batch).  These shapes run the LDS-patch kernel; tile 64 / split-K / ops.kernel_flags(no_patch=True) force the generic
-    im2col-gather kernel, so the invariance checks also compare the two kernels."""
+    training batch).  The planner's own route here is mostly Winograd F(4x4); with that off these shapes run the LDS-patch
+    kernel; tile hint 2 (64 x 64) / split-K / ops.kernel_flags(no_patch=True) force the generic im2col-gather kernel, so the
+    invariance checks compare the three kernels - and say which instance each launch ran."""
     x, w, b = _conv_case(Cin, Cout, B=B, H=H)
     y = ops.conv2d_fwd_raw(x, w, b)
+    tol = 2e-5 * (9 * Cin) ** 0.5
+    # (0) the launches compared below are the kernels they are meant to be (ops.GemmProfiler keys: name, tile, split, vec)
+    prof = ops.PROFILER = ops.GemmProfiler()
+    try:
+        y_tile64 = ops.conv2d_fwd_raw(x, w, b, tile_hint=2)
+        with ops.kernel_flags(no_wino=True):
+            y_patch = ops.conv2d_fwd_raw(x, w, b)
+    finally:
+        ops.PROFILER = None
+    (name64, tile64, _, vec64), (name_patch, _, _, _) = (r[0] for r in prof.records)
+    assert (name64, tile64, vec64) == ("conv_fwd", 64, 4)                # the generic engine on 64-wide tiles
+    # (launches of fewer than 192 patch workgroups stay on the generic engine: the planner's rule, not this test's)
+    assert name_patch == ("conv_fwd" if (Cin, Cout, B, H) in ((64, 96, 130, 8), (128, 96, 512, 4)) else f"conv_fwd_patch_w{H}")
+    assert (y_patch - y_tile64).abs().max().item() < tol                   # LDS-patch kernel against the generic 64 x 64 engine
+    assert (y_patch - y).abs().max().item() < tol
     # (1) spot check 64 output pixels x all channels against an fp64 dot product over the 3x3xCin patch
     gi = torch.Generator().manual_seed(0)
     xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
@@ -50,8 +66,7 @@ def test_conv_fwd_full_size_properties(ops, Cin, Cout, B, H):
         ref = (wk * patch[None]).sum((1, 2, 3)) + b.double()
         assert torch.allclose(y[n, i, j].double(), ref, atol=2e-5 * (9 * Cin) ** 0.5), (n, i, j)
     # (2) the plan does not change the result beyond fp32 summation order: tile 64, split-K 2, tap-major K order
-    tol = 2e-5 * (9 * Cin) ** 0.5
-    assert (ops.conv2d_fwd_raw(x, w, b, tile_hint=64) - y).abs().max().item() < tol
+    assert (y_tile64 - y).abs().max().item() < tol
     assert (ops.conv2d_fwd_raw(x, w, b, splitk_hint=2) - y).abs().max().item() < tol
     with ops.kernel_flags(no_patch=True, tap_major_k=True):
         y_tapmajor = ops.conv2d_fwd_raw(x, w, b)
