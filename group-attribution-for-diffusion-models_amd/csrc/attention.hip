@@ -553,6 +553,144 @@ __global__ __launch_bounds__(NTW) void attn_fwd_wide_f32_kernel(const AttnDev p)
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// forward for ONE HEAD OF 512 (the mid-block attention of AutoencoderKL / VQModel): the wide kernel's shape - 8 waves, wave
+// (w4, dh) owns 16 queries and one half of the head dim, partial scores meet through LDS - with the streamed tile halved to
+// KV5 = 16 keys: a 32-key K tile of 516-float rows is 66 KB, so double-buffered K and V would want 264 KB of the CU's 160;
+// at 16 keys the four tiles take 132 KB + 4 KB of exchange and the workgroup has the CU to itself.  Per wave: 64 fragment
+// registers (its half of q) + 64 accumulator registers (16 output tiles), K fragments read a float4 at a time.  The score's
+// k-sum runs as two interleaved MFMA chains per half (a single chain of 64 dependent MFMAs would wait on itself).
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int KV5 = 16;
+template <int D>
+struct Cfg5 {
+  static constexpr int TILE = (KV5 * Cfg<D>::S * 4 + 1023) / 1024 * 256;   // floats per LDS tile (whole 1 KiB DMA pieces)
+  static constexpr int NPIECE = TILE / 256;
+  static constexpr int XCH = 2 * 4 * 64 * 4;                               // exchange [half][w4][lane][4]
+  static constexpr int LDS_BYTES = (4 * TILE + XCH) * (int)sizeof(float);
+  static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
+};
+template <int D>
+__global__ __launch_bounds__(NTW) void attn_fwd_d512_f32_kernel(const AttnDev p) {
+  using C = Cfg<D>;
+  using C5 = Cfg5<D>;
+  static_assert(D % 32 == 0, "both halves are whole 16-wide tiles");
+  constexpr int G16H = C::G16 / 2, NDVH = C::NDV / 2;
+  extern __shared__ __attribute__((aligned(16))) float lds[];     // [2][K tile | V tile] | exchange
+  float* const xch = lds + 4 * C5::TILE;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int w4 = wave & 3, dh = wave >> 2;
+  const int bh = blockIdx.x / p.nblk, blk = blockIdx.x - bh * p.nblk, b = bh / p.heads, h = bh - b * p.heads;
+  const float* Q = p.q + b * p.sq + h * p.d + dh * (D / 2);
+  const float* K = p.k + b * p.sk + h * p.d;
+  const float* V = p.v + b * p.sv + h * p.d;
+  const int row = blk * 64 + w4 * 16 + c;
+
+  float qf[C::KS / 2];
+  row_frag_global<D / 2>(Q, p.ldq, row, row < p.Tq, p.scale * LOG2E, qf);
+  f32x4 o[NDVH];
+#pragma unroll
+  for (int i = 0; i < NDVH; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m = NEG_BIG, l = 0.f;
+
+  constexpr int NP8 = (C5::NPIECE + 7) / 8;
+  int koff[NP8], voff[NP8];
+#pragma unroll
+  for (int i = 0; i < NP8; ++i) {
+    const int piece = wave + 8 * i;
+    const int f = (piece * 64 + lane) * 4;
+    const int r = f / C::S, col = f - r * C::S;
+    const bool ok = piece < C5::NPIECE && r < KV5 && col < D;
+    koff[i] = ok ? r * p.ldk + col : -1;
+    voff[i] = ok ? r * p.ldv + col : -1;
+  }
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  auto stage = [&](float* buf, int row0) {
+    const bool whole = row0 + KV5 <= p.Tk;
+#pragma unroll
+    for (int i = 0; i < NP8; ++i) {
+      const int piece = wv + 8 * i;
+      if (piece < C5::NPIECE) {
+        const int f = (piece * 64 + lane) * 4;
+        const int r = f / C::S;
+        const bool okk = koff[i] >= 0 && (whole || row0 + r < p.Tk);
+        glds16(okk ? K + (long)row0 * p.ldk + koff[i] : (const float*)g_attn_zero, buf + piece * 256);
+        glds16(okk ? V + (long)row0 * p.ldv + voff[i] : (const float*)g_attn_zero, buf + C5::TILE + piece * 256);
+      }
+    }
+  };
+  const int ntiles = (p.Tk + KV5 - 1) / KV5;
+  stage(lds, 0);
+  barrier_after_dma();
+
+  for (int it = 0; it < ntiles; ++it) {
+    const float* kt_ = lds + (it & 1) * (2 * C5::TILE);
+    const float* vt_ = kt_ + C5::TILE;
+    if (it + 1 < ntiles) stage(lds + ((it + 1) & 1) * (2 * C5::TILE), (it + 1) * KV5);
+    // partial S^T[key][q] over this wave's half of the head dim, 16 keys
+    f32x4 s;
+    {
+      f32x4 sa = f32x4{0.f, 0.f, 0.f, 0.f}, sb = sa;
+      const float* kp = kt_ + c * C::S + dh * (D / 2) + 4 * g;
+#pragma unroll
+      for (int grp = 0; grp < G16H; grp += 2) {
+        const f32x4 ka = *reinterpret_cast<const f32x4*>(kp + 16 * grp);
+        const f32x4 kb = *reinterpret_cast<const f32x4*>(kp + 16 * grp + 16);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          sa = mfma16(ka[j], qf[4 * grp + j], sa);
+          sb = mfma16(kb[j], qf[4 * grp + 4 + j], sb);
+        }
+      }
+      s = sa + sb;
+    }
+    *reinterpret_cast<f32x4*>(xch + ((dh * 4 + w4) * 64 + lane) * 4) = s;
+    __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0) only: the next tile's LDS-DMA stays in flight across this barrier
+    __builtin_amdgcn_s_barrier();
+    s = *reinterpret_cast<const f32x4*>(xch + ((0 * 4 + w4) * 64 + lane) * 4) +
+        *reinterpret_cast<const f32x4*>(xch + ((1 * 4 + w4) * 64 + lane) * 4);
+    if ((it + 1) * KV5 > p.Tk) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (it * KV5 + 4 * g + e >= p.Tk) s[e] = -__builtin_inff();
+    }
+    {
+      float mx = xmax16_32(fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])));
+      if (__builtin_amdgcn_ballot_w64(mx > m + RESCALE_SLACK) != 0) {
+        const float mn = fmaxf(m, mx);
+        const float alpha = ex2(m - mn);
+        m = mn;
+        l *= alpha;
+#pragma unroll
+        for (int i = 0; i < NDVH; ++i) o[i] *= alpha;
+      }
+      float ps = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float pe = ex2(s[e] - m);
+        s[e] = pe;
+        ps += pe;
+      }
+      l += ps;
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float* vrow = vt_ + (4 * g + e) * C::S + dh * (D / 2) + c;
+#pragma unroll
+      for (int i = 0; i < NDVH; ++i) o[i] = mfma16(vrow[16 * i], s[e], o[i]);
+    }
+    barrier_after_dma();
+  }
+  float* O = p.o + b * p.so + h * p.d + dh * (D / 2);
+  const float lt = xsum16_32(l);
+  const float inv = 1.f / lt;
+  if (row < p.Tq) {
+#pragma unroll
+    for (int i = 0; i < NDVH; ++i) *reinterpret_cast<f32x4*>(O + (long)row * p.ldo + 16 * i + 4 * g) = o[i] * inv;
+    if (dh == 0 && g == 0 && p.lse) p.lse[(long)bh * p.Tq + row] = m + __builtin_amdgcn_logf(lt);
+  }
+}
+
 // delta[b, h, q] = sum_dv dO[b, q, h, dv] * O[b, q, h, dv]
 template <int D, bool RG = false>
 __global__ void attn_delta_kernel(const AttnDev p, float* delta) {
@@ -1892,6 +2030,31 @@ extern "C" int gad_attention_uses_bf16(const gad_attention_args* a, int32_t back
 }
 extern "C" int gad_attention_fwd(const gad_attention_args* a, void* stream) { return launch(a, FORWARD, IO_F32, stream, "gad_attention_fwd"); }
 extern "C" int gad_attention_bwd(const gad_attention_args* a, void* stream) { return launch(a, BACKWARD, IO_F32, stream, "gad_attention_bwd"); }
+// ---- one head of 512 (the autoencoders' mid block, gad/vae.py): its own entry point, the router above stays as it is ---------------------------
+extern "C" int gad_attention_d512_supported(int32_t d) { return d == 512; }
+extern "C" int gad_attention_fwd_d512(const gad_attention_args* a, void* stream) {
+  const char* who = "gad_attention_fwd_d512";
+  GAD_CHECK(a && a->q && a->k && a->v && a->o, "%s: null pointer", who);
+  GAD_CHECK(a->B > 0 && a->heads > 0 && a->Tq > 0 && a->Tk > 0, "%s: bad shape B=%d heads=%d Tq=%d Tk=%d", who, a->B, a->heads, a->Tq, a->Tk);
+  GAD_CHECK(gad_attention_d512_supported(a->d), "%s: head dim %d is not 512 (1..256: gad_attention_fwd)", who, a->d);
+  const long w = (long)a->heads * a->d;
+  GAD_CHECK(a->ldq >= w && a->ldk >= w && a->ldv >= w && a->ldo >= w, "%s: a row stride is smaller than heads*d = %ld", who, w);
+  GAD_CHECK((long)a->B * a->heads * gad_ceil_div(a->Tq, 64) < (1L << 31), "%s: B*heads*blocks exceeds the grid", who);
+  GAD_CHECK(a->operand_precision == 0, "%s: operand_precision must be 0 (exact fp32 only)", who);
+  GAD_CHECK(a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->ldv % 4 == 0 && a->ldo % 4 == 0 && a->stride_q % 4 == 0 && a->stride_k % 4 == 0 &&
+            a->stride_v % 4 == 0 && a->stride_o % 4 == 0, "%s: row and batch strides must be multiples of 4 floats", who);
+  GAD_CHECK(gad_aligned16(a->q) && gad_aligned16(a->k) && gad_aligned16(a->v) && gad_aligned16(a->o), "%s: q / k / v / o must be 16-byte aligned", who);
+  // the staging offsets (row * ld + column inside a tile, below 16 * ld) are 32-bit
+  GAD_CHECK((long)KV5 * a->ldk < (1L << 31) && (long)KV5 * a->ldv < (1L << 31), "%s: a row stride is too large", who);
+  static unsigned lds_set = 0;
+  if (set_lds(attn_fwd_d512_f32_kernel<512>, Cfg5<512>::LDS_BYTES, who, &lds_set)) return 1;
+  AttnDev d = make_dev(a);
+  const dim3 grid = grid_of(d, d.Tq, 64);
+  hipLaunchKernelGGL((attn_fwd_d512_f32_kernel<512>), grid, dim3(NTW), Cfg5<512>::LDS_BYTES, (hipStream_t)stream, d);
+  GAD_LAUNCH_CHECK(who);
+  return 0;
+}
+
 // bf16 q / k / v / o / d_o / dq / dk / dv (fp32 lse / delta): the bf16-operand kernels with 16-bit loads / stores
 extern "C" int gad_h_attention_fwd(const gad_attention_args* a, void* stream) { return launch(a, FORWARD, IO_BF16, stream, "gad_h_attention_fwd"); }
 extern "C" int gad_h_attention_bwd(const gad_attention_args* a, void* stream) { return launch(a, BACKWARD, IO_BF16, stream, "gad_h_attention_bwd"); }

@@ -75,10 +75,12 @@ class FusedSampler:
     from ``torch.Generator().manual_seed(b)`` on the host (bit-identical noise), but `fuse` of them
     are stacked along N so the contraction kernels see M = fuse*batch_size*H*W rows.  The U-Net
     has no cross-sample op (GroupNorm and attention are per sample), so every sample sees the same arithmetic (up to
-    the fp32 summation order of the tile / split plan picked for the launch width)."""
+    the fp32 summation order of the tile / split plan picked for the launch width).
+    `decode` (optional): NHWC x_0 of a fused group -> the NHWC tensor the image post-processing sees (an LDM pipeline's
+    VQ-VAE decode); None leaves the output as it is."""
 
-    def __init__(self, unet: UNet2DModel, scheduler: DDIMScheduler, batch_size=32, fuse=32):
-        self.unet, self.sch, self.bs, self.fuse = unet, scheduler, batch_size, fuse
+    def __init__(self, unet: UNet2DModel, scheduler: DDIMScheduler, batch_size=32, fuse=32, decode=None):
+        self.unet, self.sch, self.bs, self.fuse, self.decode = unet, scheduler, batch_size, fuse, decode
         self.device = unet.device
 
     def initial_noise(self, counters: Sequence[int], sizes: Sequence[int]) -> torch.Tensor:
@@ -88,9 +90,8 @@ class FusedSampler:
                              dtype=torch.float32) for c, n in zip(counters, sizes)]
         return ops.nchw_to_nhwc_raw(torch.cat(parts, 0).to(self.device))
 
-    def denoise_steps(self, x: torch.Tensor, num_inference_steps: int):
-        """Generator form of `denoise`: yields after every enqueued DDIM step (the pipelined scheduler interleaves another
-        coalition's training steps there), returns the NHWC images in [0,1]."""
+    def latent_steps(self, x: torch.Tensor, num_inference_steps: int):
+        """The DDIM trajectory alone: yields after every enqueued step, returns x (updated in place) = x_0, NHWC."""
         sch = self.sch
         sch.set_timesteps(num_inference_steps)
         clip = float(sch.config.clip_sample_range) if sch.config.clip_sample else 0.0
@@ -102,8 +103,14 @@ class FusedSampler:
                 a_t, a_p = sch.step_coefficients(ts)
                 ops.ddim_step_raw(x, eps, a_t, a_p, clip, out=x)
             yield
+        return x
+
+    def denoise_steps(self, x: torch.Tensor, num_inference_steps: int):
+        """Generator form of `denoise`: yields after every enqueued DDIM step (the pipelined scheduler interleaves another
+        coalition's training steps there), returns the NHWC images in [0,1]."""
+        x = yield from self.latent_steps(x, num_inference_steps)
         with torch.no_grad():
-            return ops.to_image01_raw(x)
+            return ops.to_image01_raw(x if self.decode is None else self.decode(x))
 
     def denoise(self, x: torch.Tensor, num_inference_steps: int) -> torch.Tensor:
         """x NHWC noise -> NHWC images in [0,1] after the full DDIM trajectory."""

@@ -833,6 +833,66 @@ def l2_normalize_rows_raw(x2d):
     return x2d
 
 
+# ---- eval launches of the autoencoders (gad/vae.py)
+def conv_direct_raw(x, w_krsc, bias, stride=1, pad=(1, 1, 1, 1), upsample=False, residual=None):
+    """x [B,H,W,Cin] * weights already laid out [Cout][KH][KW][Cin] -> [B,Ho,Wo,Cout] (+ residual of that shape); pad = (top,
+    bottom, left, right); `upsample`: the nearest-2x of x is folded into the gather.  Exact fp32, direct route (no Winograd
+    operand)."""
+    Bn, H, W, ci = x.shape
+    co, kh, kw, wc = w_krsc.shape
+    if wc != ci:
+        raise _capi.GadError(f"conv weight expects {wc} input channels, got {ci}")
+    He, We = (2 * H, 2 * W) if upsample else (H, W)
+    Ho, Wo = _conv_out_size(He, kh, stride, pad[0], pad[1]), _conv_out_size(We, kw, stride, pad[2], pad[3])
+    y = torch.empty((Bn, Ho, Wo, co), device=x.device, dtype=torch.float32)
+    if residual is not None and tuple(residual.shape) != tuple(y.shape):
+        raise _capi.GadError(f"conv residual {tuple(residual.shape)} does not match the output {tuple(y.shape)}")
+    gemm_raw(x, w_krsc, y, A_CONV, B_KC, Bn * Ho * Wo, co, kh * kw * ci, 0, kh * kw * ci, co,
+             geom=ConvGeom(H, W, ci, ci, Ho, Wo, kh, kw, stride, pad[0], pad[2], int(upsample)), bias=bias,
+             residual=residual, ldr=co, force_f32=True)
+    return y
+
+
+def group_norm_raw(x, gamma, beta, G, eps, silu):
+    """[SiLU](GroupNorm(x)) on contiguous NHWC [B, ..., C] (forward only, no autograd)"""
+    _req(x, "groupnorm x")
+    y = torch.empty_like(x)
+    mean = torch.empty((x.shape[0], G), device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    a = _gn_args(x, y, gamma, beta, mean, rstd, G, eps, silu)
+    check(_capi.load().gad_groupnorm_silu_fwd(C.byref(a), _stream()), "gad_groupnorm_silu_fwd")
+    return y
+
+
+def attention_d512_ok(d: int) -> bool:
+    return bool(_capi.load().gad_attention_d512_supported(int(d)))
+
+
+def attention_fwd_d512_raw(q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse=False):
+    """`attention_fwd_raw` for the wide head the autoencoders' mid block has (d = 512): exact fp32, forward only.
+    -> (o [Bn, Tq, heads*d], lse [Bn, heads, Tq] or None)"""
+    o = torch.empty((Bn, Tq, heads * d), device=q.device, dtype=torch.float32)
+    lse = torch.empty((Bn, heads, Tq), device=q.device, dtype=torch.float32) if need_lse else None
+    a = _attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, Tq * ldq, Tk * ldk, Tk * ldv)
+    check(_capi.load().gad_attention_fwd_d512(C.byref(a), _stream()), "gad_attention_fwd_d512")
+    return o, lse
+
+
+def vq_lookup_raw(z2d, codebook):
+    """z2d [n, D] (a row-strided view is read in place: NHWC latents), codebook [K, D] contiguous
+    -> (idx int32 [n] of the nearest code, zq [n, D] = z + (codebook[idx] - z))"""
+    n, D = z2d.shape
+    if z2d.dtype != torch.float32 or codebook.dtype != torch.float32 or not codebook.is_contiguous() or (D > 1 and z2d.stride(1) != 1):
+        raise _capi.GadError("vq_lookup: fp32 rows with unit column stride and a contiguous fp32 codebook are required")
+    if codebook.ndim != 2 or codebook.shape[1] != D:
+        raise _capi.GadError(f"vq_lookup: codebook {tuple(codebook.shape)} does not hold codes of {D}")
+    idx = torch.empty((n,), device=z2d.device, dtype=torch.int32)
+    zq = torch.empty((n, D), device=z2d.device, dtype=torch.float32)
+    check(_capi.load().gad_vq_lookup(z2d.data_ptr(), z2d.stride(0) if n > 1 else D, codebook.data_ptr(), n, codebook.shape[0], D,
+                                     idx.data_ptr(), zq.data_ptr(), D, _stream()), "gad_vq_lookup")
+    return idx, zq
+
+
 def layernorm_fwd_raw(x, gamma, beta, eps):
     """over the last axis of a contiguous tensor -> (y, mean [rows], rstd [rows])"""
     C_ = x.shape[-1]

@@ -32,6 +32,8 @@ class DDPMPipeline:
     def _decode(self, x_nhwc):
         return x_nhwc
 
+    decoder = None            # LDMPipeline with a VQ-VAE: latents -> [0,1] images, for whoever scores decoded samples
+
     def _run_steps(self, x, num_inference_steps, generator=None):
         """x: NHWC device tensor, updated in place through all timesteps."""
         sch = self.scheduler
@@ -124,6 +126,28 @@ class LDMPipeline(DDPMPipeline):
         lat = ops.nhwc_to_nchw_raw(x_nhwc) / float(getattr(self.vqvae.config, "scaling_factor", 1.0))
         img = self.vqvae.decode(lat).sample
         return ops.nchw_to_nhwc_raw(img.to(torch.float32).contiguous())
+
+    @property
+    def decoder(self):
+        return LatentDecoder(self) if self.vqvae is not None else None
+
+
+class LatentDecoder:
+    """[N,C,h,w] latents as the pipeline samples and the latent dataset stores them (times scaling_factor) -> [N,3,H,W]
+    images in [0,1] through the pipeline's own decode and post-processing; `tag` names the weights behind it."""
+
+    def __init__(self, pipeline, batch=64):
+        self.pipeline, self.batch = pipeline, batch
+        self.tag = getattr(pipeline.vqvae, "tag", type(pipeline.vqvae).__name__)
+
+    @torch.no_grad()
+    def __call__(self, latents_nchw):
+        p = self.pipeline
+        out = []
+        for s in range(0, len(latents_nchw), self.batch):
+            x = ops.nchw_to_nhwc_raw(latents_nchw[s:s + self.batch].to(p.device, torch.float32).contiguous())
+            out.append(ops.to_image01_raw(p._decode(x)).permute(0, 3, 1, 2))
+        return torch.cat(out, 0)
 
 
 class DDIMPipeline(DDPMPipeline):

@@ -268,13 +268,16 @@ def global_scores_against_dataset(images01, dataset, device, batch_size=512, fea
             "feature_extractor": tag}
 
 
-def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_size=256, feature_dims=768, max_ref=2000):
+def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_size=256, feature_dims=768, max_ref=2000,
+                              decode=None):
     """The CelebA global behaviour unlearn.py writes (:787-803): entropy / cluster_count / cluster_proportions of
     calculate_diversity_score (diversity_score.py:82-188) - Ward clusters of the reference embeddings, generated samples
     assigned to the nearest cluster mean, log2 entropy of the proportions.  The BLIP-VQA vision tower (hub-fetched, :89-90)
     is replaced by the seeded stand-in extractor unless `diversity_extractor` names the real one; the reference set ({OUTDIR}/celeba/cluster_imgs there) is the training
     set itself (its first `max_ref` items), mapped to [0,1] like the pipeline output.  Embeddings are computed on the
-    device; the Ward linkage stays scipy on the host, as in the reference."""
+    device; the Ward linkage stays scipy on the host, as in the reference.
+    `decode` (a pipeline's `decoder`: latents [N,C,h,w] -> [N,3,H,W] in [0,1], with a `tag`): `images01` are decoded samples,
+    so the reference latents are decoded the same way before they are embedded, and the row's tag gains `;dec=<tag>`."""
     from src.attributions.global_scores.diversity_score import diversity_from_embeddings
     net = resolve("diversity", device, lambda: FeatureNet(feature_dims, seed=4321).to(device))
     standin = isinstance(net, FeatureNet)
@@ -283,9 +286,12 @@ def diversity_against_dataset(images01, dataset, device, num_cluster=20, batch_s
         f = compute_features_torch(net, images, batch_size, device).double()
         return (torch.nn.functional.normalize(f, dim=1) if standin else f).cpu().numpy()
     rkey = ("div_ref", id(dataset)) if standin else ("div_ref", id(dataset), net.tag)
+    if decode is not None:
+        rkey = (*rkey, "dec", decode.tag)
     if rkey not in _REF_STATS:
         idx = list(range(min(len(dataset), max_ref)))
-        _REF_STATS[rkey] = embed(dataset.device_tensor(device, idx).add(1).div(2).clamp(0, 1))
+        ref = dataset.device_tensor(device, idx)
+        _REF_STATS[rkey] = embed(ref.add(1).div(2).clamp(0, 1) if decode is None else decode(ref))
     entropy, cluster_count, proportions, _, _ = diversity_from_embeddings(_REF_STATS[rkey], embed(images01.to(device)), num_cluster)
     return {"entropy": entropy, "cluster_count": cluster_count, "cluster_proportions": proportions,
-            "feature_extractor": extractor_tag(net)}
+            "feature_extractor": extractor_tag(net) if decode is None else f"{extractor_tag(net)};dec={decode.tag}"}

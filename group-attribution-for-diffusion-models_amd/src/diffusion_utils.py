@@ -88,11 +88,35 @@ def build_pipeline(args, model, backend=None):
             raise NotImplementedError("celeba samples in latent space: pass --precompute_stage reuse (no VQ-VAE weights here)")
         sc = {k: v for k, v in dataset_config("celeba")["scheduler_config"].items() if not k.startswith("_")}
         pipe_cls = getattr(be, "LDMPipeline", None)
-        pipeline = (pipe_cls(unet=model, vqvae=None, scheduler=be.DDIMScheduler(**sc)) if pipe_cls is not None
+        vqvae = celeba_vqvae(be, args.device)
+        if vqvae is not None and pipe_cls is None:
+            raise NotImplementedError("GAD_VQVAE_WEIGHTS is set, and this backend has no LDMPipeline to attach the VQ-VAE to")
+        pipeline = (pipe_cls(unet=model, vqvae=vqvae, scheduler=be.DDIMScheduler(**sc)) if pipe_cls is not None
                     else be.DDPMPipeline(unet=model, scheduler=be.DDIMScheduler(**sc))).to(args.device)
-        return pipeline, None, None
+        return pipeline, vqvae, None
     pipeline = be.DDPMPipeline(unet=model, scheduler=be.DDIMScheduler()).to(args.device)
     return pipeline, None, None
+
+
+_VQVAE = {}
+
+
+def celeba_vqvae(backend, device):
+    """`GAD_VQVAE_WEIGHTS=/path`: the CelebA-HQ VQ-VAE (`CompVis/ldm-celebahq-256`'s `vqvae` state dict, .pt or .safetensors) at
+    the registry's `vqvae_config`, re-attached before sampling as the reference does (unlearn.py:753-758, with
+    `scaling_factor = 1`); one object per (file, device) and process.  Unset: None, and everything stays in latent space."""
+    path = os.environ.get("GAD_VQVAE_WEIGHTS")
+    if not path:
+        return None
+    cls = getattr(backend, "VQModel", None)
+    if cls is None or not hasattr(cls, "from_file"):
+        raise NotImplementedError("GAD_VQVAE_WEIGHTS is set, and this backend has no VQModel to load it into")
+    key = (os.path.abspath(path), str(device), cls)
+    if key not in _VQVAE:
+        vq = cls.from_file(path, "CELEBA_VQ").to(device)
+        vq.config.scaling_factor = 1.0
+        _VQVAE[key] = vq
+    return _VQVAE[key]
 
 
 def generate_images(args, pipeline, fuse=32):
@@ -100,10 +124,11 @@ def generate_images(args, pipeline, fuse=32):
     with b; every image goes through the uint8 round trip of the PNG writer (:344-355).  Returns a float
     tensor [n,3,H,W] of k/255 values.
 
-    A `gad` DDPM/DDIM/latent-LDM pipeline (DDIM scheduler, no VQ-VAE decode) takes the engine's fused-batch sampler:
+    A `gad` DDPM/DDIM/LDM pipeline (DDIM scheduler) takes the engine's fused-batch sampler:
     `fuse` reference batches - each with its own CPU-generator seed, exactly as below - are stacked per U-Net launch
-    (the U-Net has no cross-sample op), which is what the benchmarked throughput is measured with.  Any other
-    pipeline (the oracle backend of the CPU tests, a VQ-VAE-decoding LDM) runs batch by batch."""
+    (the U-Net has no cross-sample op), which is what the benchmarked throughput is measured with; an LDM pipeline that
+    carries a `gad.VQModel` keeps the fused sampler on the latents and decodes each fused group.  Any other
+    pipeline (the oracle backend of the CPU tests, an LDM with a foreign VQ-VAE module) runs batch by batch."""
     fused = _fused_sampler_for(pipeline, args.batch_size, fuse)
     if fused is not None:
         return fused.generate(args.n_samples, args.num_inference_steps).float()
@@ -150,13 +175,16 @@ def _fused_sampler_for(pipeline, batch_size, fuse):
         from gad.coalition import FusedSampler
     except Exception:
         return None
-    if not isinstance(pipeline, gad.DDPMPipeline) or getattr(pipeline, "vqvae", None) is not None:
+    if not isinstance(pipeline, gad.DDPMPipeline):
+        return None
+    vqvae = getattr(pipeline, "vqvae", None)
+    if vqvae is not None and not isinstance(vqvae, gad.VQModel):
         return None
     if not isinstance(pipeline.scheduler, gad.DDIMScheduler) or not isinstance(pipeline.unet, gad.UNet2DModel):
         return None
     if pipeline.unet.device.type != "cuda" or fuse <= 1:
         return None
-    return FusedSampler(pipeline.unet, pipeline.scheduler, batch_size, fuse)
+    return FusedSampler(pipeline.unet, pipeline.scheduler, batch_size, fuse, decode=None if vqvae is None else pipeline._decode)
 
 
 def run_inference(model, ema_model, config, args, backend=None):

@@ -38,7 +38,7 @@ if _HERE not in sys.path:
 
 import src.constants as constants  # noqa: E402
 from src.ddpm_config import PromptConfig  # noqa: E402
-from text_to_image.compute_model_behaviors import LatentScorer, ScriptedDecoder, latents_to_uint8  # noqa: E402
+from text_to_image.compute_model_behaviors import LatentScorer, decoder_setting, latents_to_uint8, make_decoder  # noqa: E402
 
 PIXEL, CLIP = "pixel_similarity", "clip_similarity"
 PIXEL_STANDIN_TAG = "standin-latent-pixels"
@@ -81,11 +81,16 @@ def parse_args(argv=None, description="Run simple baselines for data attribution
 def network_settings(file_vars, train_pixels, what):
     """What the environment asks of a program that needs the files `file_vars` (beside --train_pixels), checked before anything
     is loaded (pure host code) -> None for the stand-ins (nothing set), else {variable: path or None}; None as a path is the
-    seeded architecture (GAD_SD_SCORER=clip-seeded; GAD_VAE_DECODER_TS has no seeded form).  Anything in between is refused."""
+    seeded architecture (GAD_SD_SCORER=clip-seeded; GAD_VAE_DECODER_TS has no seeded form).  Anything in between is refused.
+    GAD_VAE_WEIGHTS (the VAE's state dict, decoded on the HIP operators) stands wherever GAD_VAE_DECODER_TS does: its path is
+    reported under that name, `make_decoder` knows which it is; both at once are refused."""
     kind = os.environ.get("GAD_SD_SCORER")
     if kind and kind != "clip-seeded":
         raise ValueError(f"GAD_SD_SCORER={kind!r}: the only value is 'clip-seeded'")
+    decoder = decoder_setting()
     paths = {v: os.environ.get(v) or None for v in file_vars}
+    if "GAD_VAE_DECODER_TS" in paths and decoder is not None:
+        paths["GAD_VAE_DECODER_TS"] = decoder[1]
     seedable = [v for v in file_vars if v != "GAD_VAE_DECODER_TS"]
     if not kind and not any(paths.values()) and not train_pixels:
         return None
@@ -213,11 +218,11 @@ def run(args, which, backend=None):
                          "q": torch.stack([scorer.embed(lat) for lat in gen_lat]).contiguous()}
             tags[CLIP] = LatentScorer.TAG
     else:
-        decoder = ScriptedDecoder(settings["GAD_VAE_DECODER_TS"], device)
+        decoder = make_decoder(device)
         decoded = [decoder(lat) for lat in gen_lat]                            # (uint8 [H,W,3] host, [1,3,H,W] in [0,1] device)
         gen_u8 = torch.from_numpy(np.stack([u8 for u8, _ in decoded])).to(device)
         if tuple(gen_u8.shape[1:]) != tuple(train_px.shape[1:]):
-            raise ValueError(f"GAD_VAE_DECODER_TS decodes to {tuple(gen_u8.shape[1:])}, --train_pixels holds {tuple(train_px.shape[1:])}")
+            raise ValueError(f"{decoder_setting()[0]} decodes to {tuple(gen_u8.shape[1:])}, --train_pixels holds {tuple(train_px.shape[1:])}")
         train_u8 = torch.from_numpy(train_px).to(device)                       # resident as uint8: a quarter of the fp32 bytes
         if PIXEL in which:
             tags[PIXEL] = f"pixels;{decoder.tag}"

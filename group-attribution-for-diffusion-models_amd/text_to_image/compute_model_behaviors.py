@@ -20,6 +20,8 @@ Where the published files exist the stand-ins give way (nothing changes while no
   GAD_VAE_DECODER_TS=/path/decoder.pt   a TorchScript module mapping latents [B,4,h,w], already divided by the VAE's scaling
       factor (0.18215) by this caller, to images in [-1, 1]; stock torch ops, off the hand-written path, like
       GAD_FEATURE_NET_TS.  `ssim` and `nrmse` then run on the decoded uint8 images, and --img_dir stores them too.
+  GAD_VAE_WEIGHTS=/path/vae.safetensors   the VAE's own state dict (diffusers' AutoencoderKL keys, .pt or .safetensors): the
+      same decode on the HIP operators (gad/vae.py), accepted wherever GAD_VAE_DECODER_TS is; setting both is refused.
   GAD_CLIP_B32_WEIGHTS, GAD_CLIP_L14_WEIGHTS, GAD_AESTHETIC_WEIGHTS (all three, with a decoder: four-channel latents are not
       images)   OpenAI CLIP ViT-B/32, open-CLIP ViT-L-14 (openai weights) and LAION's nn.Linear(768, 1) head on the HIP
       operators (gad/vit.py): `clip_similarity` is the B/32 cosine of the two decoded images, `clip_prompt_score` the B/32
@@ -173,19 +175,55 @@ def scorer_settings(prompt_embeds=None):
     kind = os.environ.get("GAD_SD_SCORER")
     if kind and kind != "clip-seeded":
         raise ValueError(f"GAD_SD_SCORER={kind!r}: the only value is 'clip-seeded'")
+    decoder = decoder_setting()                                # (both decoder variables at once: refused here)
     weights = {v: os.environ.get(v) for v in WEIGHT_VARS}
     if not kind and not any(weights.values()):
         return None
     if not kind and not all(weights.values()):
         raise ValueError("the CLIP scorers need all of " + ", ".join(WEIGHT_VARS) + "; not set: "
                          + ", ".join(v for v, p in weights.items() if not p))
-    if not os.environ.get("GAD_VAE_DECODER_TS"):
+    if decoder is None:
         raise ValueError("the CLIP image towers score images, and four-channel latents are not images: set GAD_VAE_DECODER_TS "
-                         "to a TorchScript VAE decoder")
+                         "to a TorchScript VAE decoder (or GAD_VAE_WEIGHTS to the VAE's state dict)")
     if prompt_embeds is None or "clip_prompt" not in prompt_embeds:
         raise ValueError("the CLIP text tower is not part of this project: with the CLIP scorers the --prompt_embeds file must "
                          "carry the prompt's CLIP ViT-B/32 text embedding under the key 'clip_prompt'")
     return {"weights": weights if all(weights.values()) else None}
+
+
+def decoder_setting():
+    """Which VAE decoder the environment names, as pure host code -> None, ("GAD_VAE_DECODER_TS", path) or
+    ("GAD_VAE_WEIGHTS", path); both at once are refused before anything loads."""
+    ts, hip = os.environ.get("GAD_VAE_DECODER_TS"), os.environ.get("GAD_VAE_WEIGHTS")
+    if ts and hip:
+        raise ValueError("GAD_VAE_DECODER_TS and GAD_VAE_WEIGHTS are both set: they name the same decoder twice (a TorchScript "
+                         "export and the state dict for the HIP operators) - set one")
+    if ts:
+        return "GAD_VAE_DECODER_TS", ts
+    return ("GAD_VAE_WEIGHTS", hip) if hip else None
+
+
+def make_decoder(device):
+    """the decoder `decoder_setting` names (None: none) - an object with ScriptedDecoder's call protocol and a `tag`"""
+    setting = decoder_setting()
+    if setting is None:
+        return None
+    return (ScriptedDecoder if setting[0] == "GAD_VAE_DECODER_TS" else HipDecoder)(setting[1], device)
+
+
+class HipDecoder:
+    """`GAD_VAE_WEIGHTS`: ScriptedDecoder's protocol on gad.AutoencoderKL (the SD VAE preset, HIP operators)."""
+
+    def __init__(self, path, device, preset="SD_VAE"):
+        from gad.vae import AutoencoderKL
+        self.vae = AutoencoderKL.from_file(path, preset).to(device)
+        self.tag = self.vae.tag
+
+    @torch.no_grad()
+    def __call__(self, lat):
+        x = (self.vae.decode(lat.float() / VAE_SCALING).sample / 2 + 0.5).clamp(0, 1)
+        u8 = (x * 255).round()
+        return u8[0].permute(1, 2, 0).to(torch.uint8).cpu().numpy(), (u8 / 255).contiguous()
 
 
 class ScriptedDecoder:
@@ -298,7 +336,7 @@ def main(args, backend=None):
     pipe = backend.StableDiffusionLatentPipeline(unet)
     noise_sched = backend.DDPMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                         num_train_timesteps=1000)
-    decoder = ScriptedDecoder(os.environ["GAD_VAE_DECODER_TS"], device) if os.environ.get("GAD_VAE_DECODER_TS") else None
+    decoder = make_decoder(device)
     scorer = LatentScorer(device) if settings is None else ClipScorer(settings, pe["clip_prompt"], device)
     ref_gen = torch.Generator(device=device).manual_seed(args.seed)            # :200-201,216-219
     gen = torch.Generator(device=device).manual_seed(args.seed)

@@ -87,7 +87,9 @@ def main(args, backend=None):
     t0 = time.time()
     images = generate_images(args, pipeline)
     if args.dataset == "celeba":
-        info.update(backend.diversity_against_dataset(images, dataset, device, num_cluster=20))
+        decode = getattr(pipeline, "decoder", None)        # GAD_VQVAE_WEIGHTS: decoded samples against decoded reference latents
+        info.update(backend.diversity_against_dataset(images, dataset, device, num_cluster=20,
+                                                      **({} if decode is None else {"decode": decode})))
     elif hasattr(backend, "global_scores_against_dataset"):
         sc = backend.global_scores_against_dataset(images, dataset, device, args.batch_size)
         info.update(sc)

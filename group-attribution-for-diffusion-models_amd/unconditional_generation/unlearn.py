@@ -196,7 +196,9 @@ def main(args, backend=None):
         print(f"Generating {args.n_samples}...")
         images = generate_images(args, pipeline)
         if args.dataset == "celeba":                               # entropy, cluster_count, cluster_proportions (:787-803)
-            info.update(backend.diversity_against_dataset(images, dataset, device, num_cluster=20))
+            decode = getattr(pipeline, "decoder", None)        # GAD_VQVAE_WEIGHTS: decoded samples against decoded reference latents
+            info.update(backend.diversity_against_dataset(images, dataset, device, num_cluster=20,
+                                                          **({} if decode is None else {"decode": decode})))
             print(f"entropy: {info['entropy']}")
         elif hasattr(backend, "global_scores_against_dataset"):      # fid_value, is, precision, recall (:807-837)
             info.update(backend.global_scores_against_dataset(images, dataset, device, args.batch_size))

@@ -285,6 +285,14 @@ int gad_attention_supported(int32_t d);      /* 1 if 1 <= d <= 256 */
 int gad_attention_uses_bf16(const gad_attention_args* a, int32_t backward);   /* 1 if this launch multiplies bf16 operands */
 int gad_attention_fwd(const gad_attention_args* a, void* stream);
 int gad_attention_bwd(const gad_attention_args* a, void* stream);
+/* Forward for one wide head, d = 512 (gad_attention_d512_supported): the mid-block attention of AutoencoderKL / VQModel
+ * (gad/vae.py), one head over the whole channel count.  The contract of gad_attention_fwd's LDS-DMA launches - exact fp32,
+ * online softmax, no score tensor in memory, any Tq and Tk >= 1, ld >= heads*d so q, k, v may be column blocks of one
+ * [B*T][3C] projection, optional lse - with every ld and stride a multiple of 4 floats and every pointer 16-byte aligned;
+ * anything else (another d, operand_precision != 0, a misaligned operand) is refused by name.  8 waves per workgroup of 64
+ * queries, each with one half of the head dim; K and V stream in 16-key tiles (132 KB of LDS: one workgroup per CU). */
+int gad_attention_d512_supported(int32_t d);   /* 1 if d == 512 */
+int gad_attention_fwd_d512(const gad_attention_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Row softmax (attention probabilities), in place allowed.
@@ -701,6 +709,18 @@ enum gad_sim_x_kind { GAD_SIM_X_F32 = 0, GAD_SIM_X_U8 = 1 };
 int64_t gad_cosine_rows_workspace_bytes(int64_t N, int64_t M, int64_t D, int32_t x_kind, int32_t splits);
 int gad_cosine_rows(const void* X, int32_t x_kind, int64_t ldx, const float* lut, const float* Q, int64_t ldq, float* sim,
                     int64_t N, int64_t M, int64_t D, int32_t splits, void* ws, int64_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------
+ * VQModel's codebook lookup (csrc/vae.hip; diffusers VectorQuantizer.forward).  z: n rows of D floats (NHWC latents, row stride
+ * ldz), e: the codebook [K][D], dense.  Per row:
+ *   idx[r] = argmin_k sum_c (z[r][c] - e[k][c])^2     fp32, exact-difference form, summed in channel order, unfused;
+ *                                                     codes scanned in increasing k with a strict <: ties go to the lowest k
+ *   zq[r][c] = z[r][c] + (e[idx[r]][c] - z[r][c])     the value of the straight-through z + (z_q - z).detach(), row stride ldzq
+ * 1 <= D <= 16, K >= 1, ldz and ldzq >= D; zq must not overlap z.  A row holding a NaN gets index 0 and NaN outputs and
+ * disturbs no other row.  One thread per row, the codebook streamed through LDS in 48 KB chunks; no atomics.
+ * ---------------------------------------------------------------------------- */
+int gad_vq_lookup(const float* z, int64_t ldz, const float* e, int64_t n, int32_t K, int32_t D, int32_t* idx, float* zq,
+                  int64_t ldzq, void* stream);
 
 #ifdef __cplusplus
 }
