@@ -25,6 +25,9 @@
 // (7 products).  Either way every output element is produced in a fixed order - no float atomics, so a training step
 // stays bit-reproducible (tests/test_gpu_fullsize.py relies on that).
 //
+// Causal self-attention over at most 128 tokens (the CLIP text towers) has its own forward kernel and entry point,
+// gad_attention_causal_fwd: K and V of one (batch, head) staged whole, the tiles above the diagonal skipped.
+//
 // Any head dim <= 256 and any alignment: launches that cannot stream 16-byte pieces (the pruned CelebA model's d = 23 in
 // 322-float rows) run the `RG` instances of the same kernels - dword staging through registers, masks at d.
 #include "gad_common.h"
@@ -1678,6 +1681,118 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_bf16_kernel(const AttnDev p) 
     }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// causal forward for short sequences (the CLIP text towers, gad/text.py: T = 77, d = 64, 8 or 12 heads): query i sees keys
+// j <= i.  T <= 128, so the K and V of one (b, h) fit LDS whole (2 x 128 x 68 floats = 68 KB at most): one workgroup per
+// (b, h) of ceil(T / 16) waves stages both once by LDS-DMA ([TP][S] images, TP = T rounded up to 16, zeros beyond d / T), then
+// wave w owns queries [16 w, 16 w + 16) and reads key tiles 0 .. w only - the tiles above the diagonal are never computed.
+// A row has at most 128 keys, so its scores stay in registers (8 tiles x 4) and the softmax is one pass: max, exp2, sum.
+// Same transposed orientation as above: S^T = K Q^T, the probabilities are the B operand of O^T += V^T P^T as they stand.
+// The diagonal tile is the exception: there P is zero above the diagonal, and an MFMA would multiply those zeros with the V
+// rows of keys the query must not see (0 x NaN = NaN, for all 16 queries of the tile), so its 16 x 16 x d product runs on the
+// vector ALUs with a select per (key, query) - a masked key's V never enters the arithmetic of a query before it.
+// ------------------------------------------------------------------------------------------------------------------
+constexpr int CAUSAL_MAX_T = 128;
+constexpr int NTC = 64 * (CAUSAL_MAX_T / 16);
+template <int D>
+static int causal_image_floats(int T) { return (int)gad_ceil_div(gad_ceil_div(T, 16) * 16 * Cfg<D>::S, 256) * 256; }   // whole 1 KiB DMA pieces
+
+template <int D>
+__global__ __launch_bounds__(NTC) void attn_causal_f32_kernel(const AttnDev p, const int image) {
+  using C = Cfg<D>;
+  extern __shared__ __attribute__((aligned(16))) float lds[];     // [K image | V image]
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), nwave = (int)(blockDim.x >> 6);
+  const int lane = threadIdx.x & 63, c = lane & 15, g = lane >> 4;
+  const int bh = blockIdx.x, b = bh / p.heads, h = bh - b * p.heads, T = p.Tq;
+  const float* Q = p.q + b * p.sq + h * D;
+  const float* K = p.k + b * p.sk + h * D;
+  const float* V = p.v + b * p.sv + h * D;
+  float* kimg = lds;
+  float* vimg = lds + image;
+
+  for (int piece = wave; piece < image / 256; piece += nwave) {
+    const int f = (piece * 64 + lane) * 4;
+    const int row = f / C::S, col = f - row * C::S;
+    const bool ok = row < T && col < D;
+    glds16(ok ? K + (long)row * p.ldk + col : (const float*)g_attn_zero, kimg + piece * 256);
+    glds16(ok ? V + (long)row * p.ldv + col : (const float*)g_attn_zero, vimg + piece * 256);
+  }
+  const int q0 = 16 * wave, row = q0 + c;
+  float qf[C::KS];
+  row_frag_global<D>(Q, p.ldq, row, row < T, p.scale * LOG2E, qf);     // scores in the exp2 domain
+  barrier_after_dma();
+
+  // S^T[key][q] for the key tiles at and below the diagonal (wave-uniform guards: s stays in registers)
+  f32x4 s[CAUSAL_MAX_T / 16];
+#pragma unroll
+  for (int kt = 0; kt < CAUSAL_MAX_T / 16; ++kt) {
+    s[kt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (kt <= wave) {
+      float kf[C::KS];
+      row_frag_lds<D>(kimg, 16 * kt, kf);
+#pragma unroll
+      for (int st = 0; st < C::KS; ++st) s[kt] = mfma16(kf[st], qf[st], s[kt]);
+    }
+  }
+  // the diagonal tile: keys after the query and the padded keys j >= T leave by a select, before the row maximum
+  f32x4 sd = s[0];
+#pragma unroll
+  for (int kt = 1; kt < CAUSAL_MAX_T / 16; ++kt)
+    if (kt == wave) sd = s[kt];
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+    if (4 * g + e > c || q0 + 4 * g + e >= T) sd[e] = -__builtin_inff();
+  float mx = fmaxf(fmaxf(sd[0], sd[1]), fmaxf(sd[2], sd[3]));          // key q0 is live for every query of the tile: no empty row
+#pragma unroll
+  for (int kt = 0; kt < CAUSAL_MAX_T / 16 - 1; ++kt)
+    if (kt < wave) mx = fmaxf(mx, fmaxf(fmaxf(s[kt][0], s[kt][1]), fmaxf(s[kt][2], s[kt][3])));
+  const float m = xmax16_32(mx);
+  float l = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    sd[e] = ex2(sd[e] - m);             // exp2(-inf) = 0 exactly
+    l += sd[e];
+  }
+  f32x4 o[C::NDV];
+#pragma unroll
+  for (int i = 0; i < C::NDV; ++i) o[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int kt = 0; kt < CAUSAL_MAX_T / 16 - 1; ++kt)
+    if (kt < wave) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float pe = ex2(s[kt][e] - m);
+        l += pe;
+        const float* vrow = vimg + (16 * kt + 4 * g + e) * C::S + c;
+#pragma unroll
+        for (int i = 0; i < C::NDV; ++i) o[i] = mfma16(vrow[16 * i], pe, o[i]);
+      }
+    }
+  // diagonal tile on the vector ALUs: lane (c, g) holds O^T[dv = 16 i + 4 g + r][q = c] and needs P[key j][q = c] of all 16
+  // keys (lane c + 16 (j >> 2), register j & 3) against V[q0 + j][16 i + 4 g .. + 3]
+#pragma unroll
+  for (int j = 0; j < 16; ++j) {
+    const float pj = __shfl(sd[j & 3], c + 16 * (j >> 2), 64);
+    const bool live = j <= c;
+    const float* vr = vimg + (q0 + j) * C::S + 4 * g;
+#pragma unroll
+    for (int i = 0; i < C::NDV; ++i) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(vr + 16 * i);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[i][r] = live ? fmaf(pj, v[r], o[i][r]) : o[i][r];
+    }
+  }
+
+  const float lt = xsum16_32(l);
+  const float inv = 1.f / lt;
+  if (row < T) {                        // rows past T of the last query tile are not stored
+    float* O = p.o + b * p.so + h * D + (long)row * p.ldo;
+#pragma unroll
+    for (int i = 0; i < C::NDV; ++i) store_cols<D, false>(O, 16 * i + 4 * g, o[i] * inv, D);
+    if (g == 0 && p.lse) p.lse[(long)bh * T + row] = m + __builtin_amdgcn_logf(lt);   // v_log_f32 = log2
+  }
+}
+
 // Kernels that want more than 64 KiB of dynamic LDS need the attribute once per kernel instance and device - not per
 // launch (a driver call on the sampling / training hot path, and one made inside hipGraph captures of the U-Net).
 template <typename F>
@@ -2053,6 +2168,41 @@ extern "C" int gad_attention_fwd_d512(const gad_attention_args* a, void* stream)
   hipLaunchKernelGGL((attn_fwd_d512_f32_kernel<512>), grid, dim3(NTW), Cfg5<512>::LDS_BYTES, (hipStream_t)stream, d);
   GAD_LAUNCH_CHECK(who);
   return 0;
+}
+
+// ---- causal self-attention over at most 128 tokens (the text towers, gad/text.py): its own entry point as well ----------------------------------
+namespace {
+template <int D>
+static int launch_causal(const gad_attention_args* a, hipStream_t st, const char* who) {
+  static unsigned lds_set = 0;
+  const int image = causal_image_floats<D>(a->Tq), bytes = 2 * image * (int)sizeof(float);
+  if (set_lds(attn_causal_f32_kernel<D>, 2 * causal_image_floats<D>(CAUSAL_MAX_T) * (int)sizeof(float), who, &lds_set)) return 1;
+  AttnDev d = make_dev(a);
+  hipLaunchKernelGGL((attn_causal_f32_kernel<D>), dim3((unsigned)(a->B * a->heads)), dim3(64 * (unsigned)gad_ceil_div(a->Tq, 16)), bytes, st, d, image);
+  GAD_LAUNCH_CHECK(who);
+  return 0;
+}
+}  // namespace
+extern "C" int gad_attention_causal_supported(int32_t T, int32_t d) { return T >= 1 && T <= CAUSAL_MAX_T && (d == 16 || d == 32 || d == 64); }
+extern "C" int gad_attention_causal_fwd(const gad_attention_args* a, void* stream) {
+  const char* who = "gad_attention_causal_fwd";
+  GAD_CHECK(a && a->q && a->k && a->v && a->o, "%s: null pointer", who);
+  GAD_CHECK(a->B > 0 && a->heads > 0 && a->Tq > 0 && a->Tk > 0, "%s: bad shape B=%d heads=%d Tq=%d Tk=%d", who, a->B, a->heads, a->Tq, a->Tk);
+  GAD_CHECK(a->Tq == a->Tk, "%s: self-attention only, Tq=%d != Tk=%d", who, a->Tq, a->Tk);
+  GAD_CHECK(a->Tq <= CAUSAL_MAX_T, "%s: T=%d exceeds %d tokens", who, a->Tq, CAUSAL_MAX_T);
+  GAD_CHECK(gad_attention_causal_supported(a->Tq, a->d), "%s: head dim %d is not 16, 32 or 64", who, a->d);
+  const long w = (long)a->heads * a->d;
+  GAD_CHECK(a->ldq >= w && a->ldk >= w && a->ldv >= w && a->ldo >= w, "%s: a row stride is smaller than heads*d = %ld", who, w);
+  GAD_CHECK((long)a->B * a->heads < (1L << 31), "%s: B*heads exceeds the grid", who);
+  GAD_CHECK(a->operand_precision == 0, "%s: operand_precision must be 0 (exact fp32 only)", who);
+  GAD_CHECK(a->ldq % 4 == 0 && a->ldk % 4 == 0 && a->ldv % 4 == 0 && a->ldo % 4 == 0 && a->stride_q % 4 == 0 && a->stride_k % 4 == 0 &&
+            a->stride_v % 4 == 0 && a->stride_o % 4 == 0, "%s: row and batch strides must be multiples of 4 floats", who);
+  GAD_CHECK(gad_aligned16(a->q) && gad_aligned16(a->k) && gad_aligned16(a->v) && gad_aligned16(a->o), "%s: q / k / v / o must be 16-byte aligned", who);
+  switch (a->d) {
+    case 16: return launch_causal<16>(a, (hipStream_t)stream, who);
+    case 32: return launch_causal<32>(a, (hipStream_t)stream, who);
+    default: return launch_causal<64>(a, (hipStream_t)stream, who);
+  }
 }
 
 // bf16 q / k / v / o / d_o / dq / dk / dv (fp32 lse / delta): the bf16-operand kernels with 16-bit loads / stores

@@ -19,3 +19,4 @@ from .local import LocalBehaviors, local_model_behaviors  # noqa: F401,E402
 from .influence import InfluenceUnlearner  # noqa: F401,E402
 from .similarity import cosine_rows, group_aggregate, write_baselines  # noqa: F401,E402
 from .vae import AutoencoderKL, VQModel  # noqa: F401,E402
+from .text import CLIPTextModel, CLIPTokenizer, TextTower  # noqa: F401,E402

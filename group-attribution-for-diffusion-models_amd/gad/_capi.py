@@ -142,6 +142,8 @@ SIGNATURES = {
     "gad_attention_bwd": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
     "gad_attention_d512_supported": (C.c_int, [_i32]),
     "gad_attention_fwd_d512": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
+    "gad_attention_causal_supported": (C.c_int, [_i32, _i32]),
+    "gad_attention_causal_fwd": (C.c_int, [C.POINTER(AttentionArgs), _vp]),
     "gad_softmax_fwd": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _vp]),
     "gad_softmax_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _f32, _vp]),
     "gad_layernorm_workspace_bytes": (_i64, [_i64, _i32]),
@@ -219,6 +221,8 @@ SIGNATURES = {
     "gad_vit_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     "gad_gelu": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp]),
     "gad_l2_normalize_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp]),
+    "gad_text_tokens": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "gad_gather_rows": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _vp]),
     # similarity baselines (csrc/similarity.hip)
     "gad_cosine_rows_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32]),
     "gad_cosine_rows": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp]),

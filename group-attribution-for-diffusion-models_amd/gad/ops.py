@@ -878,6 +878,62 @@ def attention_fwd_d512_raw(q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_ls
     return o, lse
 
 
+# ---- eval launches of the text towers (gad/text.py)
+def attention_causal_ok(T: int, d: int) -> bool:
+    return bool(_capi.load().gad_attention_causal_supported(int(T), int(d)))
+
+
+def attention_causal_fwd_raw(q, k, v, Bn, heads, T, d, ldq, ldk, ldv, need_lse=False):
+    """Causal self-attention (query i sees keys j <= i) on [Bn, T, *] views, exact fp32, forward only: T <= 128, d in
+    {16, 32, 64}; q, k, v may be column blocks of one projection output as for `attention_fwd_raw`.  An unsupported launch is
+    an error.  -> (o [Bn, T, heads*d], lse [Bn, heads, T] or None)"""
+    o = torch.empty((Bn, T, heads * d), device=q.device, dtype=torch.float32)
+    lse = torch.empty((Bn, heads, T), device=q.device, dtype=torch.float32) if need_lse else None
+    a = _attention_args(q, k, v, o, lse, Bn, heads, T, T, d, ldq, ldk, ldv, T * ldq, T * ldk, T * ldv)
+    check(_capi.load().gad_attention_causal_fwd(C.byref(a), _stream()), "gad_attention_causal_fwd")
+    return o, lse
+
+
+def attention_causal_qkv_raw(qkv, Bn, T, Cq, heads):
+    """`attention_causal_fwd_raw` on the output of ONE fused projection [Bn*T, 3*Cq] (q | k | v along the columns), read in place"""
+    _req(qkv, "causal attention qkv")
+    d, ld = Cq // heads, 3 * Cq
+    return attention_causal_fwd_raw(qkv[:, 0:Cq], qkv[:, Cq:2 * Cq], qkv[:, 2 * Cq:3 * Cq], Bn, heads, T, d, ld, ld, ld)[0]
+
+
+def text_tokens_raw(ids, token_emb, pos):
+    """ids [B, T] integers (host or device), token_emb [V, W], pos [T, W] -> [B*T, W] = token_emb[ids] + pos.  An id outside
+    [0, V) is refused here, on the host (the kernel only clamps)."""
+    _req(token_emb, "text token embedding")
+    _req(pos, "text positional embedding")
+    Bn, T = ids.shape
+    V, W = token_emb.shape
+    if tuple(pos.shape) != (T, W):
+        raise _capi.GadError(f"text_tokens: {T} tokens of width {W} need a positional embedding [{T}, {W}], got {tuple(pos.shape)}")
+    host = ids.detach().cpu()
+    lo, hi = int(host.min()), int(host.max())
+    if lo < 0 or hi >= V:
+        raise _capi.GadError(f"text_tokens: token id {lo if lo < 0 else hi} is outside the vocabulary [0, {V})")
+    dev_ids = host.to(torch.int32).contiguous().to(token_emb.device)
+    out = torch.empty((Bn * T, W), device=token_emb.device, dtype=torch.float32)
+    check(_capi.load().gad_text_tokens(dev_ids.data_ptr(), token_emb.data_ptr(), pos.data_ptr(), out.data_ptr(), Bn, T, W, V, _stream()),
+          "gad_text_tokens")
+    return out
+
+
+def gather_rows_raw(x2d, rows, T):
+    """x2d [B*T, W] contiguous, rows [B] integers in [0, T) (host or device) -> [B, W]: out[b] = x2d[b*T + rows[b]]"""
+    _req(x2d, "gather_rows input")
+    Bn, W = x2d.shape[0] // T, x2d.shape[1]
+    host = rows.detach().cpu()
+    if host.numel() != Bn or int(host.min()) < 0 or int(host.max()) >= T:
+        raise _capi.GadError(f"gather_rows: {Bn} row indices in [0, {T}) are required")
+    dev_rows = host.to(torch.int32).contiguous().to(x2d.device)
+    out = torch.empty((Bn, W), device=x2d.device, dtype=torch.float32)
+    check(_capi.load().gad_gather_rows(x2d.data_ptr(), dev_rows.data_ptr(), out.data_ptr(), Bn, T, W, W, _stream()), "gad_gather_rows")
+    return out
+
+
 def vq_lookup_raw(z2d, codebook):
     """z2d [n, D] (a row-strided view is read in place: NHWC latents), codebook [K, D] contiguous
     -> (idx int32 [n] of the nearest code, zq [n, D] = z + (codebook[idx] - z))"""

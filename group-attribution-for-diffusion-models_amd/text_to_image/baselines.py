@@ -22,7 +22,8 @@ before anything is loaded.  Groups: `{cls}_{group}s.csv` against the cache's `ar
 
 Engine extras (not in the reference): --prompt_embeds, --unet_overrides, --unet_weights, --num_inference_steps,
 --guidance_scale, --device, --train_data_dir, --synthetic_cache, --train_pixels; `main(args, backend=None)`.
---dataloader_num_workers is accepted and unused (nothing is loaded per batch)."""
+--dataloader_num_workers is accepted and unused (nothing is loaded per batch).  The prompt: `--prompt_embeds`, else the text encoder
+GAD_SD_TEXT_WEIGHTS + GAD_CLIP_BPE name (gad/text.py), else the seeded stand-in."""
 import argparse
 import json
 import os
@@ -161,14 +162,9 @@ def generated_latents(args, backend, device):
     unet.to(device)
     unet.load_attn_procs(args.reference_lora_dir, weight_name="pytorch_lora_weights.safetensors")
     unet.eval()
-    if args.prompt_embeds:
-        pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False)
-        cond, uncond = pe["cond"].float(), pe["uncond"].float()
-    else:                                                                      # seeded stand-in for CLIP-text(prompt)
-        import hashlib
-        g = torch.Generator().manual_seed(int(hashlib.sha256(prompt.encode()).hexdigest()[:8], 16) % (2 ** 31))
-        ctx_dim = unet.config.cross_attention_dim
-        cond, uncond = torch.randn(77, ctx_dim, generator=g) * 0.5, torch.randn(77, ctx_dim, generator=g) * 0.5
+    from gad.text import prompt_context                                        # file > GAD_SD_TEXT_WEIGHTS' encoder > seeded stand-in
+    pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False) if args.prompt_embeds else None
+    cond, uncond, _ = prompt_context(prompt, pe, unet.config.cross_attention_dim, device)
     cond, uncond = cond.to(device).unsqueeze(0), uncond.to(device).unsqueeze(0)
     pipe = backend.StableDiffusionLatentPipeline(unet)
     gen = torch.Generator(device=device).manual_seed(args.seed)

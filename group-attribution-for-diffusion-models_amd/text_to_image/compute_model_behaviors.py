@@ -25,10 +25,15 @@ Where the published files exist the stand-ins give way (nothing changes while no
   GAD_CLIP_B32_WEIGHTS, GAD_CLIP_L14_WEIGHTS, GAD_AESTHETIC_WEIGHTS (all three, with a decoder: four-channel latents are not
       images)   OpenAI CLIP ViT-B/32, open-CLIP ViT-L-14 (openai weights) and LAION's nn.Linear(768, 1) head on the HIP
       operators (gad/vit.py): `clip_similarity` is the B/32 cosine of the two decoded images, `clip_prompt_score` the B/32
-      cosine against the prompt embedding - the text tower is not part of this project, so it is read from the
-      --prompt_embeds file's key `clip_prompt` ([embed_dim], normalised on load) - and `aesthetic_score` the head on the L/14
+      cosine against the prompt embedding - read from the --prompt_embeds file's key `clip_prompt` ([embed_dim], normalised on
+      load), or computed by the text tower when GAD_CLIP_BPE is set (below) - and `aesthetic_score` the head on the L/14
       unit embedding.  `feature_extractor` becomes the `;`-joined tags.
   GAD_SD_SCORER=clip-seeded   the same architectures with seeded weights: what the true tail costs, not what it scores.
+  GAD_CLIP_BPE=/path   the CLIP tokenizer's vocabulary (gad/clip_bpe.py).  With the CLIP scorers configured and no `clip_prompt` in
+      the --prompt_embeds file, the prompt is embedded by the B/32 text tower on the HIP operators (gad/text.py; the same
+      archive GAD_CLIP_B32_WEIGHTS names, or seeded) and `;text=<tower tag>` joins `feature_extractor`.
+  GAD_SD_TEXT_WEIGHTS=/path (with GAD_CLIP_BPE)   SD's text_encoder weights: `cond` / `uncond` that the --prompt_embeds file does
+      not carry are the encoder's hidden states of the prompt and of the empty prompt, and the row gains `prompt_encoder`.
 """
 import argparse
 import json
@@ -172,6 +177,8 @@ def scorer_settings(prompt_embeds=None):
     """What the environment asks for, checked before anything is loaded (pure host code) -> None while no CLIP variable is set
     (the stand-in scorer, whether or not a decoder is), else {"weights": {variable: path} or None for the seeded towers}.
     `prompt_embeds`: the loaded --prompt_embeds dict or None."""
+    from gad.text import sd_text_setting
+    sd_text_setting()                                          # (GAD_SD_TEXT_WEIGHTS without GAD_CLIP_BPE: refused here)
     kind = os.environ.get("GAD_SD_SCORER")
     if kind and kind != "clip-seeded":
         raise ValueError(f"GAD_SD_SCORER={kind!r}: the only value is 'clip-seeded'")
@@ -185,10 +192,11 @@ def scorer_settings(prompt_embeds=None):
     if decoder is None:
         raise ValueError("the CLIP image towers score images, and four-channel latents are not images: set GAD_VAE_DECODER_TS "
                          "to a TorchScript VAE decoder (or GAD_VAE_WEIGHTS to the VAE's state dict)")
-    if prompt_embeds is None or "clip_prompt" not in prompt_embeds:
+    text = prompt_embeds is None or "clip_prompt" not in prompt_embeds     # the prompt's embedding comes from the text tower
+    if text and not os.environ.get("GAD_CLIP_BPE"):
         raise ValueError("the CLIP text tower is not part of this project: with the CLIP scorers the --prompt_embeds file must "
                          "carry the prompt's CLIP ViT-B/32 text embedding under the key 'clip_prompt'")
-    return {"weights": weights if all(weights.values()) else None}
+    return {"weights": weights if all(weights.values()) else None, **({"text": True} if text else {})}
 
 
 def decoder_setting():
@@ -246,7 +254,7 @@ class ScriptedDecoder:
 class ClipScorer:
     """CLIP ViT-B/32 and open-CLIP ViT-L-14 + aesthetic head on the HIP operators (gad/vit.py, imported only here)."""
 
-    def __init__(self, settings, prompt, device):
+    def __init__(self, settings, prompt, device, prompt_text=None):
         from gad import vit
         w = settings["weights"]
         if w:
@@ -257,11 +265,15 @@ class ClipScorer:
             self.b32 = vit.VisionTower.seeded("clip_vit_b32").to(device)
             self.l14 = vit.VisionTower.seeded("clip_vit_l14").to(device)
             self.head = vit.AestheticHead.seeded(self.l14).to(device)
+        text_tag = None
+        if prompt is None:                                      # settings["text"]: the B/32 text tower embeds the prompt itself
+            from gad.text import clip_prompt_embedding
+            prompt, text_tag = clip_prompt_embedding(prompt_text, w["GAD_CLIP_B32_WEIGHTS"] if w else None, device)
         prompt = prompt.detach().float().reshape(-1)
         if prompt.numel() != self.b32.dims:
             raise ValueError(f"--prompt_embeds: 'clip_prompt' has {prompt.numel()} entries, the image tower embeds into {self.b32.dims}")
         self.prompt = torch.nn.functional.normalize(prompt, dim=0).to(device)
-        self.tag = ";".join((self.b32.tag, self.l14.tag, self.head.tag))
+        self.tag = ";".join((self.b32.tag, self.l14.tag, self.head.tag) + ((f"text={text_tag}",) if text_tag else ()))
 
     def embed(self, image01):
         return self.b32.embed_unit(image01)[0]
@@ -324,12 +336,8 @@ def main(args, backend=None):
         print("Pretrained model is loaded")
 
     ctx_dim = ref_unet.config.cross_attention_dim
-    if args.prompt_embeds:
-        cond, uncond = pe["cond"].float(), pe["uncond"].float()
-    else:                                                                      # seeded stand-in for CLIP-text(prompt)
-        import hashlib
-        g = torch.Generator().manual_seed(int(hashlib.sha256(prompt.encode()).hexdigest()[:8], 16) % (2 ** 31))
-        cond, uncond = torch.randn(77, ctx_dim, generator=g) * 0.5, torch.randn(77, ctx_dim, generator=g) * 0.5
+    from gad.text import prompt_context
+    cond, uncond, prompt_encoder = prompt_context(prompt, pe, ctx_dim, device)
     cond, uncond = cond.to(device).unsqueeze(0), uncond.to(device).unsqueeze(0)
 
     ref_pipe = backend.StableDiffusionLatentPipeline(ref_unet)
@@ -337,7 +345,7 @@ def main(args, backend=None):
     noise_sched = backend.DDPMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                         num_train_timesteps=1000)
     decoder = make_decoder(device)
-    scorer = LatentScorer(device) if settings is None else ClipScorer(settings, pe["clip_prompt"], device)
+    scorer = LatentScorer(device) if settings is None else ClipScorer(settings, None if settings.get("text") else pe["clip_prompt"], device, prompt)
     ref_gen = torch.Generator(device=device).manual_seed(args.seed)            # :200-201,216-219
     gen = torch.Generator(device=device).manual_seed(args.seed)
     noise_gen = torch.Generator(device=device).manual_seed(args.seed)
@@ -411,6 +419,8 @@ def main(args, backend=None):
             print(f"Checkpoint saved tp {args.ckpt_path}")
 
     row = assemble_row(args, lists, times, remaining_idx, removal_idx, tag=None if settings is None else scorer.tag)
+    if prompt_encoder is not None:
+        row["prompt_encoder"] = prompt_encoder
     with open(args.db, "a+") as f:
         f.write(json.dumps(row) + "\n")
     print(f"Results saved to the database at {args.db}")

@@ -13,7 +13,8 @@ in the reference; with fp32 activations one row per backward.
 
 Deliberate deviations: the frozen VAE / CLIP encoders are hub-fetched and outside the hot path, so `train` reads
 `{train_data_dir}/latent_cache.pt` as train_text_to_image_lora.py here does (`--synthetic_cache` writes a seeded stand-in) and
-the prompt arrives as embeddings (`--prompt_embeds`, or a seeded stand-in); generated and journey latents come from
+the prompt arrives as embeddings (`--prompt_embeds`, else the text encoder GAD_SD_TEXT_WEIGHTS + GAD_CLIP_BPE name, gad/text.py,
+else a seeded stand-in); generated and journey latents come from
 gad.StableDiffusionLatentPipeline (DDIM) with a per-step callback; noise is drawn per block of `--train_batch_size` rows as one
 [rows][k] draw from a device generator seeded with `--seed` (the reference: one draw per batch per timestep from the global
 generator); the row index of R is the offset in the flat gradient buffer (gad/trak.py)."""
@@ -115,13 +116,9 @@ def prompt_embeddings(args, ctx_dim):
         raise NotImplementedError(dataset_name(args))                     # :453-456
     assert args.cls is not None
     prompt = PromptConfig.artbench_config[args.cls]
-    if args.prompt_embeds:
-        pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False)
-        cond, uncond = pe["cond"].float(), pe["uncond"].float()
-    else:
-        import hashlib
-        g = torch.Generator().manual_seed(int(hashlib.sha256(prompt.encode()).hexdigest()[:8], 16) % (2 ** 31))
-        cond, uncond = torch.randn(77, ctx_dim, generator=g) * 0.5, torch.randn(77, ctx_dim, generator=g) * 0.5
+    from gad.text import prompt_context
+    pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False) if args.prompt_embeds else None
+    cond, uncond, _ = prompt_context(prompt, pe, ctx_dim, torch.device(args.device))   # GAD_SD_TEXT_WEIGHTS: the text encoder itself
     return cond.unsqueeze(0), uncond.unsqueeze(0)
 
 

@@ -293,6 +293,17 @@ int gad_attention_bwd(const gad_attention_args* a, void* stream);
  * queries, each with one half of the head dim; K and V stream in 16-key tiles (132 KB of LDS: one workgroup per CU). */
 int gad_attention_d512_supported(int32_t d);   /* 1 if d == 512 */
 int gad_attention_fwd_d512(const gad_attention_args* a, void* stream);
+/* Causal self-attention forward for short sequences (gad_attention_causal_supported: 1 <= T <= 128, d in {16, 32, 64}): the
+ * CLIP text towers (gad/text.py; T = 77, d = 64).  o = softmax(scale * q k^T + causal) v per (batch, head): query i sees keys
+ * j <= i.  Tq == Tk == T; exact fp32 (v_mfma_f32_16x16x4_f32), every ld and stride a multiple of 4 floats and every pointer
+ * 16-byte aligned, ld >= heads*d so q, k, v may be column blocks of one [B*T][3W] projection; lse optional, defined as for
+ * gad_attention_fwd.  Anything else (Tq != Tk, T > 128, another d, operand_precision != 0, a misaligned operand) is refused by
+ * name and launches nothing.  One workgroup per (b, h) stages K and V once in LDS (68 KB at most); key tiles above the
+ * diagonal are skipped, the diagonal tile and the padded keys j >= T are masked before the row maximum, the softmax is one
+ * pass.  A key's k and v rows never enter the arithmetic of an earlier query: a NaN at position t leaves rows < t as they were.
+ * No score or mask tensor in memory, no atomics, bit-reproducible.  o must not overlap q, k or v. */
+int gad_attention_causal_supported(int32_t T, int32_t d);
+int gad_attention_causal_fwd(const gad_attention_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Row softmax (attention probabilities), in place allowed.
@@ -685,6 +696,19 @@ int gad_vit_tokens(const float* patches, const float* cls, const float* pos, con
                    int32_t B, int32_t T, int32_t C, float eps, void* stream);
 int gad_gelu(float* x, int64_t rows, int32_t C, int32_t ld, int32_t kind, void* stream);
 int gad_l2_normalize_rows(float* x, int64_t rows, int32_t C, int32_t ld, void* stream);
+
+/* ------------------------------------------------------------------------------
+ * Text-tower gathers (csrc/text.hip; gad/text.py: CLIP's text transformers).  float4 rows: W % 4 == 0, every pointer 16-byte
+ * aligned, ldx % 4 == 0.
+ * gad_text_tokens: out[b][t][:] = token_emb[ids[b][t]][:] + pos[t][:] for ids int32 [B][T], token_emb [V][W], pos [T][W],
+ *   out [B*T][W].  The caller checks the ids (they come from the host); the kernel clamps them to [0, V) so that it never
+ *   reads outside the table.
+ * gad_gather_rows: out[b][:] = x[b*T + rows[b]][:] for x [B*T] rows of stride ldx >= W, rows int32 [B] clamped to [0, T),
+ *   out [B][W] dense (the end-of-text pooling).
+ * ---------------------------------------------------------------------------- */
+int gad_text_tokens(const int32_t* ids, const float* token_emb, const float* pos, float* out, int32_t B, int32_t T, int32_t W,
+                    int32_t V, void* stream);
+int gad_gather_rows(const float* x, const int32_t* rows, float* out, int32_t B, int32_t T, int32_t W, int64_t ldx, void* stream);
 
 /* ------------------------------------------------------------------------------
  * Similarity baselines: every cosine between training rows and generated rows in one pass (csrc/similarity.hip; reference
