@@ -131,8 +131,9 @@ typedef struct gad_gemm_args {
   /* the F(4x4, 3x3) form of the same route (output maps that are multiples of 4): B_wino4 = U[36][Cout][Cin] made by
    * gad_wino4_weights.  With both forms given the planner takes whichever models fastest (or neither); wino_ws then holds the
    * transformed input AND the 36 product panels (gad_gemm_wino_bytes covers both), ws may be needed for a split of the batched
-   * products (gad_gemm_workspace_bytes as usual).  4x fewer multiplies than the direct form; about one decimal digit less
-   * accurate than the direct fp32 kernels (still ~4e-6 of the output scale).  Large launches run the one-launch form
+   * products (gad_gemm_workspace_bytes as usual).  4x fewer multiplies than the direct form; 15-20x the error of the
+   * direct fp32 kernels on N(0, 1) data (measured 2.1e-5 .. 2.9e-5 at |y| <= 4.8, ~6e-6 of the output scale, against 1.4e-6; no
+   * more than an fp32 run of the textbook transforms loses - profiles/conv_conditioning.txt).  Large launches run the one-launch form
    * (csrc/wino4_fused.hip: all 36 products and the output transform in one kernel, wino_ws holds V only); the planner decides,
    * tile_hint 9 / 10 force the one-launch / three-launch forms (tests, A/B tools). */
   const float* B_wino4;
