@@ -1,6 +1,6 @@
-"""What the pretrained networks of the score tail (gad/inception.py, gad/vgg.py, gad/vit.py) share on the host: the digest and
-tag of a weight file, reading it, refusing a state dict by key, and the class that carries weights, tag and the chunked
-forward.  The launches themselves are the `*_raw` wrappers of gad/ops.py."""
+"""What the pretrained eval-only networks (gad/inception.py, gad/vgg.py, gad/vit.py, gad/text.py, gad/vae.py) share on the host:
+the digest and tag of a weight file, reading it, refusing a state dict by key, and the class that carries weights, tag and the
+chunked forward.  The launches themselves are the `*_raw` wrappers of gad/ops.py."""
 from __future__ import annotations
 
 import hashlib
@@ -59,9 +59,10 @@ def _to(v, device):
 
 
 class Extractor:
-    """[B,3,H,W] in [0,1] -> features [B, dims], `max_batch` images per pass.  A subclass sets `owner` (the name its refusals
-    carry), `dims`, `max_batch`, `tag`, fills `w` (tensors, tuples and dicts of them) in `load_state_dict` and runs one chunk
-    in `_chunk`."""
+    """A network whose weights sit in `w` and whose batch goes through in passes of at most `max_batch` items.  A subclass sets
+    `owner` (the name its refusals carry), `max_batch`, `tag`, and fills `w` (tensors, tuples and dicts of them) in
+    `load_state_dict`.  An image network ([B,3,H,W] in [0,1] -> features [B, `dims`]) runs one chunk in `_chunk` and inherits
+    `forward`; one with other inputs or several entry points (the text towers, the autoencoders) calls `_chunked` itself."""
 
     owner = dims = max_batch = None
 
@@ -74,12 +75,16 @@ class Extractor:
         self.w = _to(self.w, device)
         return self
 
-    @torch.no_grad()
-    def forward(self, images_nchw01):
+    def _chunked(self, fn, batch):
+        """`fn` on at most `max_batch` items of `batch` at a time -> the results along dim 0; refused without weights"""
         if not self.w:
             raise _capi.GadError(f"{self.owner}: no weights loaded")
-        outs = [self._chunk(images_nchw01[s:s + self.max_batch]) for s in range(0, len(images_nchw01), self.max_batch)]
+        outs = [fn(batch[s:s + self.max_batch]) for s in range(0, len(batch), self.max_batch)]
         return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+
+    @torch.no_grad()
+    def forward(self, images_nchw01):
+        return self._chunked(self._chunk, images_nchw01)
 
     def __call__(self, images_nchw01):
         return self.forward(images_nchw01)

@@ -868,14 +868,19 @@ def attention_d512_ok(d: int) -> bool:
     return bool(_capi.load().gad_attention_d512_supported(int(d)))
 
 
-def attention_fwd_d512_raw(q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse=False):
-    """`attention_fwd_raw` for the wide head the autoencoders' mid block has (d = 512): exact fp32, forward only.
-    -> (o [Bn, Tq, heads*d], lse [Bn, heads, Tq] or None)"""
+def _attention_eval_raw(symbol, q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse):
+    """The forward-only, exact-fp32 attention entry point `symbol` on [Bn, T, *] views -> (o, lse or None)"""
     o = torch.empty((Bn, Tq, heads * d), device=q.device, dtype=torch.float32)
     lse = torch.empty((Bn, heads, Tq), device=q.device, dtype=torch.float32) if need_lse else None
     a = _attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, Tq * ldq, Tk * ldk, Tk * ldv)
-    check(_capi.load().gad_attention_fwd_d512(C.byref(a), _stream()), "gad_attention_fwd_d512")
+    check(getattr(_capi.load(), symbol)(C.byref(a), _stream()), symbol)
     return o, lse
+
+
+def attention_fwd_d512_raw(q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse=False):
+    """`attention_fwd_raw` for the wide head the autoencoders' mid block has (d = 512): exact fp32, forward only.
+    -> (o [Bn, Tq, heads*d], lse [Bn, heads, Tq] or None)"""
+    return _attention_eval_raw("gad_attention_fwd_d512", q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse)
 
 
 # ---- eval launches of the text towers (gad/text.py)
@@ -887,11 +892,7 @@ def attention_causal_fwd_raw(q, k, v, Bn, heads, T, d, ldq, ldk, ldv, need_lse=F
     """Causal self-attention (query i sees keys j <= i) on [Bn, T, *] views, exact fp32, forward only: T <= 128, d in
     {16, 32, 64}; q, k, v may be column blocks of one projection output as for `attention_fwd_raw`.  An unsupported launch is
     an error.  -> (o [Bn, T, heads*d], lse [Bn, heads, T] or None)"""
-    o = torch.empty((Bn, T, heads * d), device=q.device, dtype=torch.float32)
-    lse = torch.empty((Bn, heads, T), device=q.device, dtype=torch.float32) if need_lse else None
-    a = _attention_args(q, k, v, o, lse, Bn, heads, T, T, d, ldq, ldk, ldv, T * ldq, T * ldk, T * ldv)
-    check(_capi.load().gad_attention_causal_fwd(C.byref(a), _stream()), "gad_attention_causal_fwd")
-    return o, lse
+    return _attention_eval_raw("gad_attention_causal_fwd", q, k, v, Bn, heads, T, T, d, ldq, ldk, ldv, need_lse)
 
 
 def attention_causal_qkv_raw(qkv, Bn, T, Cq, heads):

@@ -3,7 +3,7 @@ text_to_image/compute_model_behaviors.py:302-306, clip.tokenize + encode_text) a
 (`text_encoder(ids)[0]`, the U-Net's cross-attention context; train_text_to_image_lora.py:723-731,1055,1249,
 grad_text_to_image_lora.py:275-283, compute_model_behaviors.py:235,293-299).
 
-Eval only, fp32 throughout.  Both are one network, a pre-LN transformer under a causal mask:
+Eval only, fp32 throughout.  Both are one network, a pre-LN transformer under a causal mask (its blocks are gad/encoder.py's):
 
     x = token_emb[ids] + pos                                         gad_text_tokens              [B T][W]
     per block:  x += out_proj(causal_attn(ln_1(x) W_qkv + b))        gad_layernorm_fwd, gad_gemm, gad_attention_causal_fwd, gad_gemm
@@ -34,15 +34,13 @@ Environment (text_to_image/compute_model_behaviors.py, grad_text_to_image_lora.p
 `python -m gad.text --prompt "..." --out pe.pt` writes `cond`, `uncond` and `clip_prompt` for whichever towers are configured."""
 from __future__ import annotations
 
-import math
 import os
 from dataclasses import dataclass
 
 import torch
 
-from . import _capi, ops
-from ._capi import GELU_ERF, GELU_QUICK
-from .extractor import _to, check_state_dict, file_tag, load_checkpoint
+from . import _capi, encoder, ops
+from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
 
 
 @dataclass(frozen=True)
@@ -74,10 +72,7 @@ def _config(preset_or_config):
 
 
 def _check_config(cfg):
-    if cfg.act not in ("gelu", "quick_gelu"):
-        raise ValueError(f"TextTower: act {cfg.act!r}: use 'gelu' or 'quick_gelu'")
-    if cfg.width % cfg.heads or cfg.width % 4:
-        raise ValueError(f"TextTower: width {cfg.width} must be a multiple of heads {cfg.heads} and of 4")
+    encoder.check_config("TextTower", cfg)
     if not ops.attention_causal_ok(cfg.context, cfg.width // cfg.heads):
         raise ValueError(f"TextTower: context {cfg.context} with head dim {cfg.width // cfg.heads}: the causal attention kernel "
                          f"takes 1..128 tokens and head dims 16, 32, 64")
@@ -93,83 +88,52 @@ def _layout(preset_or_config, layout):
     return cfg, layout
 
 
+# layout names -> the tower's own, around the blocks (`blocks`: their layout in gad/encoder.py)
+_NAMES = {
+    "openai": dict(tok="token_embedding.weight", pos="positional_embedding", blocks="openai", ln_final="ln_final"),
+    "hf": dict(tok="embeddings.token_embedding.weight", pos="embeddings.position_embedding.weight", blocks="hf_split",
+               ln_final="final_layer_norm"),
+}
+
+
 def expected_shapes(preset_or_config, layout=None):
     """{state-dict key without prefix: shape} of everything `load_state_dict` reads, in the layout's own names.  `layout`:
     'openai' | 'hf'; None: the preset's, or by `embed_dim` for a plain configuration."""
     cfg, layout = _layout(preset_or_config, layout)
-    V, T, W, M = cfg.vocab, cfg.context, cfg.width, cfg.mlp
-    out = {}
+    W, n = cfg.width, _NAMES[layout]
+    out = {n["tok"]: (cfg.vocab, W), n["pos"]: (cfg.context, W)}
+    for i in range(cfg.layers):
+        out.update(encoder.block_shapes(n["blocks"], i, W, cfg.mlp))
+    out[n["ln_final"] + ".weight"], out[n["ln_final"] + ".bias"] = (W,), (W,)
     if layout == "openai":
-        out["token_embedding.weight"], out["positional_embedding"] = (V, W), (T, W)
-        for i in range(cfg.layers):
-            p = f"transformer.resblocks.{i}."
-            for n in ("ln_1", "ln_2"):
-                out[p + n + ".weight"], out[p + n + ".bias"] = (W,), (W,)
-            out[p + "attn.in_proj_weight"], out[p + "attn.in_proj_bias"] = (3 * W, W), (3 * W,)
-            out[p + "attn.out_proj.weight"], out[p + "attn.out_proj.bias"] = (W, W), (W,)
-            out[p + "mlp.c_fc.weight"], out[p + "mlp.c_fc.bias"] = (M, W), (M,)
-            out[p + "mlp.c_proj.weight"], out[p + "mlp.c_proj.bias"] = (W, M), (W,)
-        out["ln_final.weight"], out["ln_final.bias"] = (W,), (W,)
         out["text_projection"] = (W, cfg.embed_dim)
-    else:
-        out["embeddings.token_embedding.weight"], out["embeddings.position_embedding.weight"] = (V, W), (T, W)
-        for i in range(cfg.layers):
-            p = f"encoder.layers.{i}."
-            for n in ("layer_norm1", "layer_norm2"):
-                out[p + n + ".weight"], out[p + n + ".bias"] = (W,), (W,)
-            for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                out[p + f"self_attn.{n}.weight"], out[p + f"self_attn.{n}.bias"] = (W, W), (W,)
-            out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = (M, W), (M,)
-            out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (W, M), (W,)
-        out["final_layer_norm.weight"], out["final_layer_norm.bias"] = (W,), (W,)
-        if cfg.embed_dim is not None:
-            out["text_projection.weight"] = (cfg.embed_dim, W)
+    elif cfg.embed_dim is not None:
+        out["text_projection.weight"] = (cfg.embed_dim, W)
     return out
 
 
 def seeded_state_dict(preset_or_config, seed, layout=None):
-    """gad/vit.py's rules: weights N(0, 1 / fan_in) (the residual stream keeps its scale through the blocks), LayerNorm gains
-    1 + N(0, 0.1^2), every bias and embedding N(0, 0.1^2) but the positional one (0.02^2)."""
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for key, shape in expected_shapes(preset_or_config, layout).items():
-        r = torch.randn(shape, generator=g)
-        if key == "text_projection":
-            sd[key] = r / math.sqrt(shape[0])
-        elif any(n in key for n in ("ln_", "layer_norm")):
-            sd[key] = 1 + 0.1 * r if key.endswith("weight") else 0.1 * r
-        elif "position" in key:
-            sd[key] = 0.02 * r
-        elif "token_embedding" in key:
-            sd[key] = 0.1 * r
-        elif key.endswith("weight") and len(shape) > 1:
-            sd[key] = r / math.sqrt(math.prod(shape[1:]))
-        else:
-            sd[key] = 0.1 * r
-    return sd
+    """`encoder.seeded` of `expected_shapes`"""
+    return encoder.seeded(expected_shapes(preset_or_config, layout), seed)
 
 
 HF_PREFIX = "text_model."
 
 
-class TextTower:
+class TextTower(Extractor):
     """token ids [B, context] (host or device integers) -> `hidden` [B, T, W], `embed` [B, embed_dim], `embed_unit`;
     `max_batch` prompts per pass."""
 
     def __init__(self, preset_or_config, state_dict=None, tag=None):
         self.cfg, self.name = _config(preset_or_config)
         _check_config(self.cfg)
-        self.owner = f"TextTower({self.name})"
-        self.dims = self.cfg.embed_dim if self.cfg.embed_dim is not None else self.cfg.width
-        # activations alive at once per prompt, in floats: T rows of the two residual buffers, the normed copy and the attention
-        # output (4 W), the qkv projection (3 W) and the MLP hidden (mlp): B/32 77 x 5632 = 0.43 M (1.7 MB), SD's 77 x 8448 =
-        # 0.65 M (2.6 MB) -> 0.5 GB holds 309 / 206 prompts; rounded down to a power of two, capped at 256
         c = self.cfg
-        per_prompt = 4 * c.context * (7 * c.width + c.mlp)
-        self.max_batch = max(1, min(256, 1 << int(math.log2(max(1, (1 << 29) // per_prompt)))))
-        self.tag, self.w = tag or f"{self.name}-unloaded", {}
-        if state_dict is not None:
-            self.load_state_dict(state_dict)
+        self.owner = f"TextTower({self.name})"
+        self.dims = c.embed_dim if c.embed_dim is not None else c.width
+        # the blocks' activations in floats per prompt: B/32 77 x 5632 = 0.43 M (1.7 MB), SD's 77 x 8448 = 0.65 M (2.6 MB) -> 0.5 GB
+        # holds 309 / 206 prompts: 256 / 128
+        self.max_batch = encoder.max_batch(c.context, c.width, c.mlp)
+        super().__init__(tag or f"{self.name}-unloaded", state_dict)
 
     @classmethod
     def seeded(cls, preset_or_config, seed=1234):
@@ -184,10 +148,6 @@ class TextTower:
         else:
             sd = load_checkpoint(path, torchscript=True)
         return cls(preset, sd, tag=file_tag(preset, path))
-
-    def to(self, device):
-        self.w = _to(self.w, device)
-        return self
 
     def load_state_dict(self, sd):
         cfg = self.cfg
@@ -209,73 +169,45 @@ class TextTower:
         def get(k):
             return sd[prefix + k].detach().float().contiguous()
 
-        def pair(k):
-            return get(k + ".weight"), get(k + ".bias")
-
-        w = {}
+        n = _NAMES[layout]
+        w = {"tok": get(n["tok"]), "pos": get(n["pos"])}
+        for i in range(cfg.layers):
+            w[i] = encoder.load_block(get, n["blocks"], i)
+        w["ln_final"] = get(n["ln_final"] + ".weight"), get(n["ln_final"] + ".bias")
         if layout == "openai":
-            w["tok"], w["pos"] = get("token_embedding.weight"), get("positional_embedding")
-            for i in range(cfg.layers):
-                p = f"transformer.resblocks.{i}."
-                w[i] = dict(ln1=pair(p + "ln_1"), ln2=pair(p + "ln_2"), qkv=(get(p + "attn.in_proj_weight"), get(p + "attn.in_proj_bias")),
-                            out=pair(p + "attn.out_proj"), fc=pair(p + "mlp.c_fc"), proj=pair(p + "mlp.c_proj"))
-            w["ln_final"] = pair("ln_final")
             w["head"] = get("text_projection").t().contiguous()         # [embed, width]: K-contiguous like every Linear weight
-        else:
-            w["tok"], w["pos"] = get("embeddings.token_embedding.weight"), get("embeddings.position_embedding.weight")
-            for i in range(cfg.layers):
-                p = f"encoder.layers.{i}."
-                qkv = [pair(p + f"self_attn.{n}") for n in ("q_proj", "k_proj", "v_proj")]
-                w[i] = dict(ln1=pair(p + "layer_norm1"), ln2=pair(p + "layer_norm2"),
-                            qkv=(torch.cat([t[0] for t in qkv], 0).contiguous(), torch.cat([t[1] for t in qkv], 0).contiguous()),
-                            out=pair(p + "self_attn.out_proj"), fc=pair(p + "mlp.fc1"), proj=pair(p + "mlp.fc2"))
-            w["ln_final"] = pair("final_layer_norm")
-            if head is not None:
-                w["head"] = sd["text_projection.weight"].detach().float().contiguous()
+        elif head is not None:
+            w["head"] = sd["text_projection.weight"].detach().float().contiguous()
         self.w = w
         return self
 
     # ---- launches ----
-    def _ln(self, x, gb):
-        return ops.layernorm_fwd_raw(x, *gb, self.cfg.eps)[0]
-
-    def _block(self, x, Bn, blk):
-        cfg = self.cfg
-        qkv = ops.linear_fwd_raw(self._ln(x, blk["ln1"]), *blk["qkv"], force_f32=True)
-        o = ops.attention_causal_qkv_raw(qkv, Bn, cfg.context, cfg.width, cfg.heads)
-        x = ops.linear_fwd_raw(o.view(Bn * cfg.context, cfg.width), *blk["out"], residual=x, force_f32=True)
-        h = ops.linear_fwd_raw(self._ln(x, blk["ln2"]), *blk["fc"], force_f32=True)
-        h = ops.gelu_raw(h, GELU_ERF if cfg.act == "gelu" else GELU_QUICK)
-        return ops.linear_fwd_raw(h, *blk["proj"], residual=x, force_f32=True)
-
     def _trunk(self, ids):
         """ids [B, T] -> the residual stream after the last block [B T, W] (before ln_final)"""
+        cfg = self.cfg
         x = ops.text_tokens_raw(ids, self.w["tok"], self.w["pos"])
-        for i in range(self.cfg.layers):
-            x = self._block(x, ids.shape[0], self.w[i])
+        for i in range(cfg.layers):
+            x = encoder.block(x, ids.shape[0], cfg.context, cfg.width, cfg.heads, cfg.act, cfg.eps, self.w[i], ops.attention_causal_qkv_raw)
         return x
 
     def _hidden_chunk(self, ids):
-        return self._ln(self._trunk(ids), self.w["ln_final"]).view(ids.shape[0], self.cfg.context, self.cfg.width)
+        return encoder.ln(self._trunk(ids), self.w["ln_final"], self.cfg.eps).view(ids.shape[0], self.cfg.context, self.cfg.width)
 
     def _pooled_chunk(self, ids):
         rows = ids.argmax(dim=-1)                                 # the end-of-text row (see the module docstring)
-        return self._ln(ops.gather_rows_raw(self._trunk(ids), rows, self.cfg.context), self.w["ln_final"])
+        return encoder.ln(ops.gather_rows_raw(self._trunk(ids), rows, self.cfg.context), self.w["ln_final"], self.cfg.eps)
 
     def _embed_chunk(self, ids):
         return ops.linear_fwd_raw(self._pooled_chunk(ids), self.w["head"], force_f32=True)
 
     @torch.no_grad()
     def _run(self, chunk, ids):
-        if not self.w:
-            raise _capi.GadError(f"{self.owner}: no weights loaded")
         ids = torch.as_tensor(ids)
         if ids.ndim != 2 or ids.shape[1] != self.cfg.context or ids.is_floating_point():
             raise _capi.GadError(f"{self.owner}: token ids must be integers [B, {self.cfg.context}], got {ids.dtype} {tuple(ids.shape)}")
         ids = ids.detach().cpu()                                  # a few hundred integers: they are checked and pooled on the host
         with ops.operand_precision("f32"):                        # this tower is fp32 whatever the process-wide switch says
-            outs = [chunk(ids[s:s + self.max_batch]) for s in range(0, len(ids), self.max_batch)]
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
+            return self._chunked(chunk, ids)
 
     def hidden(self, ids):
         """[B, T, W] after the final LayerNorm: HF's `last_hidden_state`"""

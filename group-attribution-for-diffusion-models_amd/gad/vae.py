@@ -36,7 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _capi, ops
-from .extractor import _to, check_state_dict, file_tag, load_checkpoint
+from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
 
 EPS = 1e-6
 # gad_attention_fwd_d512 takes a CU per workgroup of 64 queries (132 KB of LDS), so below one workgroup per CU its time is
@@ -203,8 +203,9 @@ class DiagonalGaussian:
         return self.mean + self.std * noise
 
 
-class _Autoencoder:
-    kind = owner = tag_kind = None
+class _Autoencoder(Extractor):
+    """`max_batch` images per pass: a 256 x 256 x 128 activation is 32 MB per image"""
+    kind = tag_kind = None
 
     def __init__(self, config, state_dict=None, tag=None):
         if config.kind != self.kind:
@@ -213,10 +214,8 @@ class _Autoencoder:
         if not (c <= 256 or ops.attention_d512_ok(c)):
             raise _capi.GadError(f"{self.owner}: the mid block's single attention head of {c} has no kernel (1..256 or 512)")
         self.config = SimpleNamespace(**vars(config))
-        self.tag, self.w, self.max_batch = tag or f"{self.tag_kind}-unloaded", {}, 8
-        self.device = torch.device("cpu")
-        if state_dict is not None:
-            self.load_state_dict(state_dict)
+        self.max_batch, self.device = 8, torch.device("cpu")
+        super().__init__(tag or f"{self.tag_kind}-unloaded", state_dict)
 
     @classmethod
     def seeded(cls, cfg, seed=1234):
@@ -229,9 +228,8 @@ class _Autoencoder:
         return cls(cfg, load_file(path), tag=file_tag(cls.tag_kind, path))
 
     def to(self, device):
-        self.w = _to(self.w, device)
         self.device = torch.device(device)
-        return self
+        return super().to(device)
 
     # ---- weights ----
     def load_state_dict(self, sd):
@@ -257,10 +255,6 @@ class _Autoencoder:
             w["quantize.embedding"] = f(sd["quantize.embedding.weight"])
         self.w = w
         return self
-
-    def _need(self):
-        if not self.w:
-            raise _capi.GadError(f"{self.owner}: no weights loaded")
 
     # ---- launches (NHWC) ----
     def _gn(self, name, x, silu):
@@ -325,17 +319,11 @@ class _Autoencoder:
             raise _capi.GadError(f"{self.owner}: {what} expects [B, {channels}, H, W], got {tuple(x_nchw.shape)}")
         return ops.nchw_to_nhwc_raw(ops._req(x_nchw.to(self.device, torch.float32).contiguous(), what))
 
-    def _chunks(self, x_nchw, fn):
-        """fn on at most `max_batch` images at a time (a 256 x 256 x 128 activation is 32 MB per image)"""
-        self._need()
-        outs = [fn(x_nchw[s:s + self.max_batch]) for s in range(0, len(x_nchw), self.max_batch)]
-        return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
-
     @torch.no_grad()
     def encode_moments(self, x_nchw):
         """quant_conv(encoder(x)) as NCHW"""
-        return self._chunks(x_nchw, lambda x: ops.nhwc_to_nchw_raw(
-            self._conv1x1("quant_conv", self._encoder(self._nhwc(x, self.config.in_channels, "encode")))))
+        return self._chunked(lambda x: ops.nhwc_to_nchw_raw(
+            self._conv1x1("quant_conv", self._encoder(self._nhwc(x, self.config.in_channels, "encode")))), x_nchw)
 
 
 class AutoencoderKL(_Autoencoder):
@@ -344,8 +332,8 @@ class AutoencoderKL(_Autoencoder):
     @torch.no_grad()
     def decode(self, z, return_dict=True):
         """z [B, L, h, w] (already divided by scaling_factor) -> `.sample` [B, out, 8h, 8w] for four blocks"""
-        img = self._chunks(z, lambda c: ops.nhwc_to_nchw_raw(
-            self._decoder(self._conv1x1("post_quant_conv", self._nhwc(c, self.config.latent_channels, "decode")))))
+        img = self._chunked(lambda c: ops.nhwc_to_nchw_raw(
+            self._decoder(self._conv1x1("post_quant_conv", self._nhwc(c, self.config.latent_channels, "decode")))), z)
         return SimpleNamespace(sample=img) if return_dict else (img,)
 
     def encode(self, x, return_dict=True):
@@ -370,7 +358,7 @@ class VQModel(_Autoencoder):
             if not force_not_quantize:
                 x = self.lookup(x)[1]
             return ops.nhwc_to_nchw_raw(self._decoder(self._conv1x1("post_quant_conv", x)))
-        img = self._chunks(h, one)
+        img = self._chunked(one, h)
         return SimpleNamespace(sample=img) if return_dict else (img,)
 
     def encode(self, x, return_dict=True):

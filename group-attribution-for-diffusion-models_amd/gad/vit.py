@@ -3,7 +3,7 @@
 aesthetic head (`aesthetic_score`; :253-262,419-431, src/aesthetics.py) and the BLIP-VQA vision tower whose `pooler_output`
 the CelebA diversity score clusters (src/attributions/global_scores/diversity_score.py:89-120).
 
-Eval only, fp32 throughout.  The three are one network, a pre-LN Vision Transformer:
+Eval only, fp32 throughout.  The three are one network, a pre-LN Vision Transformer (its blocks are gad/encoder.py's):
 
     patches = resize + crop + patchify(images)                       gad_resize_bicubic_patches   [B g g][P P 3]
     x = LN_pre?([cls | patches W_patch' + b'] + pos)                 gad_gemm, gad_vit_tokens     [B T][W]
@@ -37,8 +37,8 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _capi, ops
-from ._capi import GELU_ERF, GELU_QUICK, check
+from . import _capi, encoder, ops
+from ._capi import check
 from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
 
 CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
@@ -88,86 +88,37 @@ def _config(preset_or_config):
     return PRESETS[preset_or_config], preset_or_config
 
 
-def _check_config(cfg):
-    if cfg.act not in ("gelu", "quick_gelu"):
-        raise ValueError(f"VisionTower: act {cfg.act!r}: use 'gelu' or 'quick_gelu'")
-    if cfg.image_size % cfg.patch or cfg.width % cfg.heads or cfg.width % 4:
-        raise ValueError(f"VisionTower: image_size {cfg.image_size} must be a multiple of patch {cfg.patch}, width {cfg.width} "
-                         f"of heads {cfg.heads} and of 4")
+# layout names -> the tower's own, around the blocks (`blocks`: their layout in gad/encoder.py); `lead`: the dimensions BLIP's
+# embeddings keep in front for broadcasting
+_NAMES = {
+    "clip": dict(prefix="visual.", patch="conv1", cls="class_embedding", pos="positional_embedding", ln_pre="ln_pre",
+                 blocks="openai", ln_post="ln_post", lead=()),
+    "blip": dict(prefix="vision_model.", patch="embeddings.patch_embedding", cls="embeddings.class_embedding",
+                 pos="embeddings.position_embedding", ln_pre="pre_layernorm", blocks="hf_fused", ln_post="post_layernorm", lead=(1,)),
+}
 
 
 def expected_shapes(preset_or_config):
     """{state-dict key without prefix: shape} of everything `load_state_dict` reads, in the layout's own names."""
     cfg, _ = _config(preset_or_config)
-    W, P, T, M = cfg.width, cfg.patch, cfg.tokens, cfg.mlp
-    out = {}
-    if cfg.layout == "clip":
-        out["conv1.weight"] = (W, 3, P, P)
-        if cfg.patch_bias:
-            out["conv1.bias"] = (W,)
-        out["class_embedding"], out["positional_embedding"] = (W,), (T, W)
-        if cfg.ln_pre:
-            out["ln_pre.weight"], out["ln_pre.bias"] = (W,), (W,)
-        for i in range(cfg.layers):
-            p = f"transformer.resblocks.{i}."
-            for n in ("ln_1", "ln_2"):
-                out[p + n + ".weight"], out[p + n + ".bias"] = (W,), (W,)
-            out[p + "attn.in_proj_weight"], out[p + "attn.in_proj_bias"] = (3 * W, W), (3 * W,)
-            out[p + "attn.out_proj.weight"], out[p + "attn.out_proj.bias"] = (W, W), (W,)
-            out[p + "mlp.c_fc.weight"], out[p + "mlp.c_fc.bias"] = (M, W), (M,)
-            out[p + "mlp.c_proj.weight"], out[p + "mlp.c_proj.bias"] = (W, M), (W,)
-        out["ln_post.weight"], out["ln_post.bias"] = (W,), (W,)
+    W, n = cfg.width, _NAMES[cfg.layout]
+    out = {n["patch"] + ".weight": (W, 3, cfg.patch, cfg.patch)}
+    if cfg.patch_bias:
+        out[n["patch"] + ".bias"] = (W,)
+    out[n["cls"]], out[n["pos"]] = 2 * n["lead"] + (W,), n["lead"] + (cfg.tokens, W)
+    if cfg.ln_pre:
+        out[n["ln_pre"] + ".weight"], out[n["ln_pre"] + ".bias"] = (W,), (W,)
+    for i in range(cfg.layers):
+        out.update(encoder.block_shapes(n["blocks"], i, W, cfg.mlp))
+    out[n["ln_post"] + ".weight"], out[n["ln_post"] + ".bias"] = (W,), (W,)
+    if cfg.embed_dim is not None:
         out["proj"] = (W, cfg.embed_dim)
-    else:
-        out["embeddings.patch_embedding.weight"] = (W, 3, P, P)
-        if cfg.patch_bias:
-            out["embeddings.patch_embedding.bias"] = (W,)
-        out["embeddings.class_embedding"], out["embeddings.position_embedding"] = (1, 1, W), (1, T, W)
-        if cfg.ln_pre:
-            out["pre_layernorm.weight"], out["pre_layernorm.bias"] = (W,), (W,)
-        for i in range(cfg.layers):
-            p = f"encoder.layers.{i}."
-            for n in ("layer_norm1", "layer_norm2"):
-                out[p + n + ".weight"], out[p + n + ".bias"] = (W,), (W,)
-            out[p + "self_attn.qkv.weight"], out[p + "self_attn.qkv.bias"] = (3 * W, W), (3 * W,)
-            out[p + "self_attn.projection.weight"], out[p + "self_attn.projection.bias"] = (W, W), (W,)
-            out[p + "mlp.fc1.weight"], out[p + "mlp.fc1.bias"] = (M, W), (M,)
-            out[p + "mlp.fc2.weight"], out[p + "mlp.fc2.bias"] = (W, M), (W,)
-        out["post_layernorm.weight"], out["post_layernorm.bias"] = (W,), (W,)
     return out
 
 
-# layout names -> the tower's own: (patch w, patch b, cls, pos, ln_pre, block prefix, ln1, ln2, qkv w, qkv b, out, fc, proj, ln_post)
-_NAMES = {
-    "clip": dict(prefix="visual.", patch="conv1", cls="class_embedding", pos="positional_embedding", ln_pre="ln_pre",
-                 block="transformer.resblocks.{}.", ln1="ln_1", ln2="ln_2", qkv_w="attn.in_proj_weight", qkv_b="attn.in_proj_bias",
-                 out="attn.out_proj", fc="mlp.c_fc", proj="mlp.c_proj", ln_post="ln_post"),
-    "blip": dict(prefix="vision_model.", patch="embeddings.patch_embedding", cls="embeddings.class_embedding",
-                 pos="embeddings.position_embedding", ln_pre="pre_layernorm", block="encoder.layers.{}.", ln1="layer_norm1",
-                 ln2="layer_norm2", qkv_w="self_attn.qkv.weight", qkv_b="self_attn.qkv.bias", out="self_attn.projection",
-                 fc="mlp.fc1", proj="mlp.fc2", ln_post="post_layernorm"),
-}
-
-
 def seeded_state_dict(preset_or_config, seed):
-    """Weights N(0, 1 / fan_in) (the residual stream keeps its scale through the blocks), LayerNorm gains 1 + N(0, 0.1^2), every
-    bias and embedding N(0, 0.1^2) but the positional one (0.02^2)."""
-    cfg, _ = _config(preset_or_config)
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for key, shape in expected_shapes(cfg).items():
-        r = torch.randn(shape, generator=g)
-        if key == "proj":
-            sd[key] = r / math.sqrt(shape[0])
-        elif any(n in key for n in ("ln_", "layer_norm", "layernorm")):
-            sd[key] = 1 + 0.1 * r if key.endswith("weight") else 0.1 * r
-        elif key.endswith("weight") and len(shape) > 1:
-            sd[key] = r / math.sqrt(math.prod(shape[1:]))
-        elif "position" in key:
-            sd[key] = 0.02 * r
-        else:
-            sd[key] = 0.1 * r
-    return sd
+    """`encoder.seeded` of `expected_shapes`"""
+    return encoder.seeded(expected_shapes(preset_or_config), seed)
 
 
 def fold_normalisation(weight, bias, mean, std):
@@ -239,16 +190,14 @@ class VisionTower(Extractor):
 
     def __init__(self, preset_or_config, state_dict=None, tag=None):
         self.cfg, self.name = _config(preset_or_config)
-        _check_config(self.cfg)
-        self.owner = f"VisionTower({self.name})"
-        self.dims = self.cfg.embed_dim if self.cfg.embed_dim is not None else self.cfg.width
-        # Activations alive at once per image, in floats: the patch matrix g g 3 P P, then T rows of the two residual
-        # buffers, the normed copy and the attention output (4 W), the qkv projection (3 W) and the MLP hidden (mlp):
-        # B/32 50 x 8448 + 150528 = 0.57 M (2.3 MB), L/14 257 x 11264 + 150528 = 3.0 M (12 MB), BLIP 577 x 8448 + 442368 =
-        # 5.3 M (21 MB) -> 0.5 GB holds 234 / 44 / 25 images; rounded down to a power of two (128 / 32 / 16), capped at 256.
         c = self.cfg
-        per_image = 4 * (c.tokens * (7 * c.width + c.mlp) + c.image_size * c.image_size * 3)
-        self.max_batch = max(1, min(256, 1 << int(math.log2(max(1, (1 << 29) // per_image)))))
+        encoder.check_config("VisionTower", c, grid=(c.image_size, c.patch))
+        self.owner = f"VisionTower({self.name})"
+        self.dims = c.embed_dim if c.embed_dim is not None else c.width
+        # the blocks' activations plus the patch matrix g g 3 P P, in floats per image: B/32 50 x 8448 + 150528 = 0.57 M (2.3 MB),
+        # L/14 257 x 11264 + 150528 = 3.0 M (12 MB), BLIP 577 x 8448 + 442368 = 5.3 M (21 MB) -> 0.5 GB holds 234 / 44 / 25 images:
+        # 128 / 32 / 16
+        self.max_batch = encoder.max_batch(c.tokens, c.width, c.mlp, extra=c.image_size * c.image_size * 3)
         super().__init__(tag or f"{self.name}-unloaded", state_dict)
 
     @classmethod
@@ -282,9 +231,7 @@ class VisionTower(Extractor):
         if cfg.ln_pre:
             w["ln_pre"] = pair(names["ln_pre"])
         for i in range(cfg.layers):
-            p = names["block"].format(i)
-            w[i] = dict(ln1=pair(p + names["ln1"]), ln2=pair(p + names["ln2"]), qkv=(get(p + names["qkv_w"]), get(p + names["qkv_b"])),
-                        out=pair(p + names["out"]), fc=pair(p + names["fc"]), proj=pair(p + names["proj"]))
+            w[i] = encoder.load_block(get, names["blocks"], i)
         w["ln_post"] = pair(names["ln_post"])
         if cfg.embed_dim is not None:
             w["head"] = get("proj").t().contiguous()           # [embed, width]: K-contiguous like every Linear weight
@@ -292,9 +239,6 @@ class VisionTower(Extractor):
         return self
 
     # ---- launches ----
-    def _ln(self, x, gb):
-        return ops.layernorm_fwd_raw(x, *gb, self.cfg.eps)[0]
-
     def tokens(self, images_nchw01):
         """[B,3,H,W] in [0,1] -> the token sequence [B T, W] in front of the first block"""
         cfg = self.cfg
@@ -308,21 +252,12 @@ class VisionTower(Extractor):
                                           out.data_ptr(), Bn, cfg.tokens, cfg.width, cfg.eps, ops._stream()), "gad_vit_tokens")
         return out
 
-    def _block(self, x, Bn, blk):
-        cfg = self.cfg
-        qkv = ops.linear_fwd_raw(self._ln(x, blk["ln1"]), *blk["qkv"], force_f32=True)
-        o = ops.attention_core_qkv_raw(qkv, Bn, cfg.tokens, cfg.width, cfg.heads)
-        x = ops.linear_fwd_raw(o.view(Bn * cfg.tokens, cfg.width), *blk["out"], residual=x, force_f32=True)
-        h = ops.linear_fwd_raw(self._ln(x, blk["ln2"]), *blk["fc"], force_f32=True)
-        h = ops.gelu_raw(h, GELU_ERF if cfg.act == "gelu" else GELU_QUICK)
-        return ops.linear_fwd_raw(h, *blk["proj"], residual=x, force_f32=True)
-
     def _chunk(self, images_nchw01):
         cfg, Bn = self.cfg, images_nchw01.shape[0]
         x = self.tokens(images_nchw01)
         for i in range(cfg.layers):
-            x = self._block(x, Bn, self.w[i])
-        pooled = self._ln(x.view(Bn, cfg.tokens, cfg.width)[:, 0].contiguous(), self.w["ln_post"])
+            x = encoder.block(x, Bn, cfg.tokens, cfg.width, cfg.heads, cfg.act, cfg.eps, self.w[i], ops.attention_core_qkv_raw)
+        pooled = encoder.ln(x.view(Bn, cfg.tokens, cfg.width)[:, 0].contiguous(), self.w["ln_post"], cfg.eps)
         return ops.linear_fwd_raw(pooled, self.w["head"], force_f32=True) if cfg.embed_dim is not None else pooled
 
     def forward(self, images_nchw01):
