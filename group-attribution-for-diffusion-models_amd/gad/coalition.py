@@ -286,7 +286,7 @@ class CoalitionEngine:
                     break
         # EMA weights are used for inference (unlearn.py:751-753); the fine-tuned ones are not kept
         model.flat[0].copy_(trainer.ema_flat)
-        ops.WEIGHT_EPOCH[0] += 1                                         # flat copy: no per-parameter version bump
+        ops.written_everywhere()                                         # flat copy: no per-parameter version bump
         model.eval()
         ev1.record()
         return dict(removal_seed=removal_seed, remaining_idx=remaining_idx, removed_idx=removed_idx, model=model, loss=loss,

@@ -18,6 +18,7 @@ import torch
 
 from . import _capi, ops
 from ._capi import GroupNormArgs, HGemmArgs, check
+from .shadows import Shadow, cached
 
 BF16 = torch.bfloat16
 
@@ -110,27 +111,18 @@ def add_raw(a, b):
 # ----------------------------------------------------------------------------------
 # weight copies
 # ----------------------------------------------------------------------------------
-def _cached(w, attr, make):
-    key = ops.weight_key(w)
-    c = getattr(w, attr, None)
-    if c is None or c[0] != key:
-        c = (key, make())
-        setattr(w, attr, c)
-    return c[1]
-
-
 def half_weight(w):
     """bf16 copy of a parameter in its storage order ([out][in] Linear, [Cout][KH][KW][Cin] conv), refreshed when the
     parameter changes (once for a frozen weight; once per optimizer step for a LoRA matrix in the flat buffer)."""
     if w.ndim == 4:
-        return _cached(w, "_gad_h", lambda: to_half(ops.weight_krsc(w).detach()))
-    return _cached(w, "_gad_h", lambda: to_half(w.detach()))
+        return cached(w, "_gad_h", lambda: to_half(ops.weight_krsc(w).detach()))
+    return cached(w, "_gad_h", lambda: to_half(w.detach()))
 
 
 def half_weight_t(w):
     """bf16 [in][out] transpose of a Linear / 1x1-conv weight: what the data gradient dx = dy W reads as B[n = in][k = out]"""
     src = w.detach().reshape(w.shape[0], -1) if w.ndim == 2 else ops.weight_krsc(w).detach().reshape(w.shape[0], -1)
-    return _cached(w, "_gad_ht", lambda: transpose_raw(src))
+    return cached(w, "_gad_ht", lambda: transpose_raw(src))
 
 
 def half_weight_rot(w):
@@ -141,33 +133,31 @@ def half_weight_rot(w):
         if not had and hasattr(w, "_gad_rot"):
             del w._gad_rot                      # the fp32 rotated copy was only a stepping stone
         return r
-    return _cached(w, "_gad_hrot", make)
+    return cached(w, "_gad_hrot", make)
 
 
-def _flat_pairs(flat):
+def _pairs_shadow(flat):
+    rows = [(off, p_.shape[0], p_.shape[1], a, b) for p_, off, _ in getattr(flat, "_gad_params", ()) if p_.ndim == 2
+            for a in range(0, p_.shape[0], 64) for b in range(0, p_.shape[1], 64)]
+    table = torch.tensor(rows, dtype=torch.int64, device=flat.device)
+    sh, sht = (torch.zeros(flat.numel(), device=flat.device, dtype=BF16) for _ in range(2))
+    flat._gad_hpairs = s = Shadow((sh, sht), lambda home: check(_capi.load().gad_h_shadow_pairs(
+        home.data_ptr(), sh.data_ptr(), sht.data_ptr(), table.data_ptr(), len(rows), _st()), "gad_h_shadow_pairs"))
+    return s
+
+
+def _flat_pairs(flat, off=None, w=None):
     """(bf16 shadow, bf16 shadow of the transposes) of every 2-D matrix resident in a flat parameter buffer, refreshed by ONE launch
-    per optimizer step (gad_h_shadow_pairs); the table of 64 x 64 tiles is built once per buffer."""
-    key = (flat._version, ops.WEIGHT_EPOCH[0], getattr(flat, "_gad_epoch", 0))
-    c = getattr(flat, "_gad_hpairs", None)
-    if c is None:
-        rows = [(off, p_.shape[0], p_.shape[1], a, b) for p_, off, _ in getattr(flat, "_gad_params", ()) if p_.ndim == 2
-                for a in range(0, p_.shape[0], 64) for b in range(0, p_.shape[1], 64)]
-        table = torch.tensor(rows, dtype=torch.int64, device=flat.device)
-        c = [None, torch.zeros(flat.numel(), device=flat.device, dtype=BF16), torch.zeros(flat.numel(), device=flat.device, dtype=BF16),
-             table, len(rows), {}]
-        flat._gad_hpairs = c
-    versions = {o_: p_._version for p_, o_, _ in getattr(flat, "_gad_params", ())}
-    if c[0] != key or c[5] != versions:
-        check(_capi.load().gad_h_shadow_pairs(flat.data_ptr(), c[1].data_ptr(), c[2].data_ptr(), c[3].data_ptr(), c[4], _st()), "gad_h_shadow_pairs")
-        c[0], c[5] = key, versions
-    return c[1], c[2]
+    per optimizer step (gad_h_shadow_pairs) - or when the resident `w` at `off` was written through torch -; the table of
+    64 x 64 tiles is built once per buffer."""
+    return (getattr(flat, "_gad_hpairs", None) or _pairs_shadow(flat)).fresh_for(flat, off, w).buffers
 
 
 def _half_of(w):
     """bf16 copy of a 2-D parameter: a slice of its flat buffer's shadow where it lives in one"""
     if ops._in_flat_buffer(w):
         flat, off, n = w._gad_flat
-        return _flat_pairs(flat)[0][off:off + n].view(w.shape)
+        return _flat_pairs(flat, off, w)[0][off:off + n].view(w.shape)
     return to_half(w.detach())
 
 
@@ -175,7 +165,7 @@ def _half_t_of(w):
     """bf16 transpose [cols][rows] of a 2-D parameter (slice of the flat buffer's transposed shadow where it lives in one)"""
     if ops._in_flat_buffer(w):
         flat, off, n = w._gad_flat
-        return _flat_pairs(flat)[1][off:off + n].view(w.shape[1], w.shape[0])
+        return _flat_pairs(flat, off, w)[1][off:off + n].view(w.shape[1], w.shape[0])
     return transpose_raw(to_half(w.detach()))
 
 
@@ -434,7 +424,7 @@ class HConv2dFn(torch.autograd.Function):
                 wr = half_weight_rot(w)
                 if Cout % 8:                      # conv_out (4 channels): the gather reads 16-byte chunks - zero-pad dy and W' to 8 channels
                     dy = torch.nn.functional.pad(dy, (0, 8 - Cout % 8))
-                    wr = _cached(w, "_gad_hrot8", lambda: torch.nn.functional.pad(wr, (0, 8 - Cout % 8)).contiguous())
+                    wr = cached(w, "_gad_hrot8", lambda: torch.nn.functional.pad(wr, (0, 8 - Cout % 8)).contiguous())
                 dxe = conv_fwd_raw(dy, wr, None, 3, 3)                                    # forward conv of dy with the rotated weight
                 if upsample:
                     dx = _empty(ctx.xshape, dy.device)

@@ -74,4 +74,4 @@ class InfluenceUnlearner:
         flat.add_(delta.to(flat.device, torch.float32), alpha=float(ratio))
         # the parameters are views with version counters of their own: what is derived from them (rotated 3x3 weights, Winograd
         # panels, bf16 casts, fused projections) keys on the buffer's epoch, as after the raw optimizer kernel
-        flat._gad_epoch = getattr(flat, "_gad_epoch", 0) + 1
+        ops.written(flat)

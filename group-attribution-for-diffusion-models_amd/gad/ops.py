@@ -17,6 +17,8 @@ import torch
 from . import _capi
 from ._capi import (A_CONV, A_CONVT, A_KC, A_MC, B_CONV, B_KC, B_MC, B_WDGRAD, AdamArgs, ConvGeom, GemmArgs,
                     GroupNormArgs, check)
+from .shadows import (WEIGHT_EPOCH, Shadow, cached, in_flat_buffer as _in_flat_buffer, weight_key, written,  # noqa: F401
+                      written_everywhere)
 
 # ----------------------------------------------------------------------------------
 # plumbing
@@ -526,36 +528,20 @@ def bf16_weight(w):
     """bf16 (RNE) copy of a conv weight in its [Cout][KH][KW][Cin] storage: the bf16-mode patch convolution streams it by
     LDS-DMA instead of rounding the fp32 weights in every workgroup.  A parameter that lives in a flat buffer
     (training.flatten_params) is served from ONE bf16 shadow of the whole buffer, refreshed by a single cast when the
-    weights changed (torch version counter, or the epoch the raw optimizer kernels bump) - so training pays one cast per
-    step, not one per layer; any other parameter caches its own copy."""
-    home = getattr(w, "_gad_flat", None)
-    if home is not None and w.data_ptr() == home[0].data_ptr() + 4 * home[1]:
-        flat, off, n = home
-        key = (flat._version, WEIGHT_EPOCH[0], getattr(flat, "_gad_epoch", 0))
-        cached = getattr(flat, "_gad_bf16", None)
-        if cached is None or cached[0] != key:
-            shadow = cached[1] if cached is not None else torch.empty(flat.numel(), device=flat.device, dtype=torch.bfloat16)
-            shadow.copy_(flat.detach())
-            # A resident parameter written through torch (load_state_dict, p.copy_(), a torch.optim step) bumps only ITS
-            # version counter, not the buffer's: remember every resident's version as of this cast ...
-            cached = (key, shadow, {o_: p_._version for p_, o_, _ in getattr(flat, "_gad_params", ())})
-            flat._gad_bf16 = cached
-        if cached[2].get(off, w._version) != w._version:          # ... and re-cast the slice of one that moved since
-            cached[1][off:off + n].copy_(flat.detach()[off:off + n])
-            cached[2][off] = w._version
+    weights changed (`Shadow.fresh_for`) - so training pays one cast per step, not one per layer; any other parameter
+    caches its own copy."""
+    if _in_flat_buffer(w):
+        flat, off, n = w._gad_flat
+        s = (getattr(flat, "_gad_bf16", None) or _bf16_shadow(flat)).fresh_for(flat, off, w)
         o, i, kh, kw = w.shape
-        return cached[1][off:off + n].view(o, kh, kw, i)
-    key = weight_key(w)
-    cached = getattr(w, "_gad_bf16", None)
-    if cached is None or cached[0] != key:
-        cached = (key, weight_krsc(w).detach().to(torch.bfloat16).contiguous())
-        w._gad_bf16 = cached
-    return cached[1]
+        return s.buffers[0][off:off + n].view(o, kh, kw, i)
+    return cached(w, "_gad_bf16", lambda: weight_krsc(w).detach().to(torch.bfloat16).contiguous())
 
 
-def _in_flat_buffer(w) -> bool:
-    home = getattr(w, "_gad_flat", None)
-    return home is not None and w.data_ptr() == home[0].data_ptr() + 4 * home[1]
+def _bf16_shadow(flat):
+    copy = torch.empty(flat.numel(), device=flat.device, dtype=torch.bfloat16)
+    flat._gad_bf16 = s = Shadow((copy,), lambda home: copy.copy_(home.detach()))
+    return s
 
 
 def dgrad_as_forward(w, stride, pad) -> bool:
@@ -570,53 +556,41 @@ def dgrad_as_forward(w, stride, pad) -> bool:
             and w.shape[1] >= 64 and (not w.requires_grad or _in_flat_buffer(w)) and not KERNEL_FLAGS.get("native_dgrad"))
 
 
-def _rot_table(flat):
-    """(device table, tiles) of `gad_rotate_conv3x3` for the 3x3 weights resident in `flat` - built once per buffer."""
-    cached = getattr(flat, "_gad_rot_table", None)
-    if cached is None:
-        rows = [(off, p_.shape[0], p_.shape[1], a, b)
-                for p_, off, _ in getattr(flat, "_gad_params", ()) if p_.ndim == 4 and tuple(p_.shape[2:]) == (3, 3)
-                for a in range(0, p_.shape[0], 32) for b in range(0, p_.shape[1], 32)]
-        cached = (torch.tensor(rows, dtype=torch.int64, device=flat.device), len(rows)) if rows else (None, 0)
-        flat._gad_rot_table = cached
-    return cached
+def _rotate_conv3x3(flat, out, table, tiles):
+    check(_capi.load().gad_rotate_conv3x3(flat.data_ptr(), out.data_ptr(), table.data_ptr(), tiles, _stream()), "gad_rotate_conv3x3")
+
+
+def _rotated_shadow(flat):
+    """The rotated shadow of a flat buffer is itself the home of further shadows (its bf16 cast, its Winograd forms): it carries
+    the 3x3 resident list with the channel roles swapped, and every refresh announces that it was written."""
+    rows = [(off, co, ci, a, b) for off, co, ci in _conv3x3_residents(flat) for a in range(0, co, 32) for b in range(0, ci, 32)]
+    table = torch.tensor(rows, dtype=torch.int64, device=flat.device)
+    out = torch.empty_like(flat)
+    out._gad_conv3x3 = [(off, ci, co) for off, co, ci in _conv3x3_residents(flat)]      # rotated: [Cin][3][3][Cout]
+
+    def refresh(home):
+        _rotate_conv3x3(home, out, table, len(rows))
+        written(out)
+    flat._gad_rot = s = Shadow((out,), refresh)
+    return s
 
 
 def rotated_weight(w):
     """W'[ci][2-r][2-s][co] = W[co][r][s][ci] as a conv parameter of logical shape [Cin, Cout, 3, 3] (storage
     [Cin][3][3][Cout]).  A weight living in a flat parameter buffer is served from ONE rotated shadow of the buffer,
-    refreshed by a single launch when the weights changed (same keys as `bf16_weight`; the returned view carries
-    `_gad_flat`, so bf16 mode casts the whole shadow once, too); any other weight caches its own copy per version."""
+    refreshed by a single launch when the weights changed (`Shadow.fresh_for`; the returned view carries `_gad_flat`, so
+    bf16 mode casts the whole shadow once, too); any other weight caches its own copy per version."""
     if _in_flat_buffer(w):
         flat, off, n = w._gad_flat
-        table, tiles = _rot_table(flat)
-        key = (flat._version, WEIGHT_EPOCH[0], getattr(flat, "_gad_epoch", 0))
-        cached = getattr(flat, "_gad_rot", None)
-        stale = cached is None or cached[0] != key
-        if not stale and cached[2].get(off, w._version) != w._version:      # written through torch since the last refresh
-            stale = True
-        if stale and tiles:
-            shadow = cached[1] if cached is not None else torch.empty_like(flat)
-            shadow._gad_conv3x3 = [(o_, b, a) for o_, a, b in _conv3x3_residents(flat)]      # rotated: [Cin][3][3][Cout]
-            check(_capi.load().gad_rotate_conv3x3(flat.data_ptr(), shadow.data_ptr(), table.data_ptr(), tiles, _stream()),
-                  "gad_rotate_conv3x3")
-            shadow._gad_epoch = getattr(shadow, "_gad_epoch", 0) + 1         # its residents changed (bf16_weight's key)
-            cached = (key, shadow, {o_: p_._version for p_, o_, _ in flat._gad_params}, cached[3] if cached is not None else {})
-            flat._gad_rot = cached
-        view = cached[3].get(off)
+        s = (getattr(flat, "_gad_rot", None) or _rotated_shadow(flat)).fresh_for(flat, off, w)
+        view = s.views.get(off)
         if view is None:
             co, ci = w.shape[0], w.shape[1]
-            view = cached[1][off:off + n].view(ci, 3, 3, co).permute(0, 3, 1, 2)
-            view._gad_flat = (cached[1], off, n)
-            cached[3][off] = view
+            view = s.views[off] = s.buffers[0][off:off + n].view(ci, 3, 3, co).permute(0, 3, 1, 2)
+            view._gad_flat = (s.buffers[0], off, n)
         return view
-    key = weight_key(w)
-    cached = getattr(w, "_gad_rot", None)
-    if cached is None or cached[0] != key:
-        store = weight_krsc(w).detach().flip(1, 2).permute(3, 1, 2, 0).contiguous()      # [Cin][KH][KW][Cout]
-        cached = (key, store.permute(0, 3, 1, 2))
-        w._gad_rot = cached
-    return cached[1]
+    # storage [Cin][KH][KW][Cout]
+    return cached(w, "_gad_rot", lambda: weight_krsc(w).detach().flip(1, 2).permute(3, 1, 2, 0).contiguous().permute(0, 3, 1, 2))
 
 
 def _conv3x3_residents(flat):
@@ -634,8 +608,10 @@ def _wino_ok(co, ci):
     return ci % 32 == 0 and co % 4 == 0 and co >= 64
 
 
-def _wino_transform(src, items, npos):
-    """items [(src offset, Cout, Cin)] -> (U buffer, {src offset: (dst offset, floats)}, table, tiles); npos = 16 or 36"""
+def _wino_shadow(src, items, f):
+    """The Winograd forms of items [(offset in src, Cout, Cin)]: U, {offset: (offset in U, floats)} and the tile table are built
+    once; f = 2 or 4.  `src` is a buffer, or a conv parameter standing for its own storage."""
+    launch, npos = (_capi.load().gad_wino_weights, 16) if f == 2 else (_capi.load().gad_wino4_weights, 36)
     rows, where, doff = [], {}, 0
     for off, co, ci in items:
         where[off] = (doff, npos * co * ci)
@@ -643,7 +619,8 @@ def _wino_transform(src, items, npos):
         doff += npos * co * ci
     U = torch.empty(max(doff, 1), device=src.device, dtype=torch.float32)
     table = torch.tensor(rows, dtype=torch.int64, device=src.device)
-    return U, where, table, len(rows)
+    return Shadow((U,), lambda home: check(launch(home.data_ptr(), U.data_ptr(), table.data_ptr(), len(rows), _stream()),
+                                           "gad_wino_weights"), where)
 
 
 def wino_weight(w, f=2):
@@ -651,45 +628,25 @@ def wino_weight(w, f=2):
     [36][Cout][Cin] for F(4x4, 3x3) (`gad_wino4_weights`, f = 4); None for a weight the Winograd kernels do not take
     (Cin % 32, Cout % 4, < 64 output channels, bf16-operand mode, the no_wino switch).  A weight living in a flat parameter
     buffer - or in the rotated shadow of one, for the data gradients - is served from ONE transformed shadow of that buffer
-    per form, refreshed by a single launch when the weights changed (the keys of `bf16_weight`); any other weight caches its
-    own transform per version."""
+    per form, refreshed by a single launch when the weights changed (`Shadow.fresh_for`); any other weight keeps its own
+    transform, rewritten in place per version."""
     co, ci = w.shape[0], w.shape[1]
     if (tuple(w.shape[2:]) != (3, 3) or not _wino_ok(co, ci) or OPERAND_PRECISION[0] >= 1
             or KERNEL_FLAGS["gemm"] & (_capi.GEMM_NO_WINO | _capi.GEMM_NO_PATCH | _capi.GEMM_SCALAR_EPILOGUE | _capi.GEMM_TAP_MAJOR_K)
             or (f == 4 and KERNEL_FLAGS.get("no_wino4"))):
         return None
-    lib = _capi.load()
-    launch, npos, attr = (lib.gad_wino_weights, 16, "_gad_wino") if f == 2 else (lib.gad_wino4_weights, 36, "_gad_wino4")
+    attr = "_gad_wino" if f == 2 else "_gad_wino4"
     if _in_flat_buffer(w):
         flat, off, n = w._gad_flat
-        key = (flat._version, WEIGHT_EPOCH[0], getattr(flat, "_gad_epoch", 0))
-        cached = getattr(flat, attr, None)
-        if cached is None:
-            items = [(o_, a, b) for o_, a, b in _conv3x3_residents(flat) if _wino_ok(a, b)]
-            cached = [None, *_wino_transform(flat, items, npos), {}]
-            setattr(flat, attr, cached)
-        _, U, where, table, tiles, versions = cached
-        if off not in where:
+        s = getattr(flat, attr, None)
+        if s is None:
+            s = _wino_shadow(flat, [it for it in _conv3x3_residents(flat) if _wino_ok(it[1], it[2])], f)
+            setattr(flat, attr, s)
+        if off not in s.where:
             return None
-        stale = cached[0] != key or versions.get(off, w._version) != w._version
-        if stale:
-            check(launch(flat.data_ptr(), U.data_ptr(), table.data_ptr(), tiles, _stream()), "gad_wino_weights")
-            cached[0] = key
-            cached[5] = {o_: p_._version for p_, o_, _ in getattr(flat, "_gad_params", ())}
-        d0, dn = where[off]
-        return U[d0:d0 + dn]
-    key = weight_key(w)
-    cached = getattr(w, attr, None)
-    if cached is None or cached[0] != key:
-        src = weight_krsc(w).detach()
-        if cached is None:
-            U, _, table, tiles = _wino_transform(src, [(0, co, ci)], npos)
-        else:
-            U, table, tiles = cached[1], cached[2], cached[3]
-        check(launch(src.data_ptr(), U.data_ptr(), table.data_ptr(), tiles, _stream()), "gad_wino_weights")
-        cached = (key, U, table, tiles)
-        setattr(w, attr, cached)
-    return cached[1]
+        d0, dn = s.where[off]
+        return s.fresh_for(flat, off, w).buffers[0][d0:d0 + dn]
+    return cached(w, attr, lambda: _wino_shadow(w, [(0, co, ci)], f), lambda s: s.refresh(weight_krsc(w))).buffers[0]
 
 
 def refresh_wino(module):
@@ -1755,22 +1712,8 @@ def sumsq_raw(g, out=None):
     return out
 
 
-# Raw kernels update parameters through device pointers, which torch's per-tensor version counters do not see.  Anything
-# that caches a function of the weights (the fused q|k|v projection of the sampling path) keys on this epoch as well.
-WEIGHT_EPOCH = [0]            # rare events that rewrite arbitrary parameters behind torch's back (EMA copy_to / restore ...)
-
-
-def weight_key(w):
-    """Cache key of anything derived from parameter `w`: its address, torch's version counter, the global epoch, and -
-    for a parameter living in a flat buffer (training.flatten_params) - that buffer's own epoch, which the raw optimizer
-    kernel bumps every step.  Frozen parameters outside the buffer (the SD base U-Net under LoRA) therefore keep their
-    derived copies (bf16 casts, rotated convolution weights) across training steps."""
-    home = getattr(w, "_gad_flat", None)
-    return (w.data_ptr(), w._version, WEIGHT_EPOCH[0], getattr(home[0], "_gad_epoch", 0) if home is not None else 0)
-
-
 def clip_adam_ema_raw(p, g, m, v, ema, sumsq, *, max_norm, lr, betas, eps, weight_decay, adamw, step, ema_decay):
-    p._gad_epoch = getattr(p, "_gad_epoch", 0) + 1        # p is the flat parameter buffer: its residents changed
+    written(p)        # p is the flat parameter buffer: a raw kernel moves its residents, which no version counter sees (gad/shadows.py)
     a = AdamArgs()
     a.p, a.g, a.m, a.v, a.ema = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _ptr(ema)
     a.n = p.numel()

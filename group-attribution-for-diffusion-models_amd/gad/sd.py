@@ -323,7 +323,7 @@ class UNet2DConditionModel(nn.Module):
                            f"(first key: {next(iter(sd))!r})")
         if left:
             raise KeyError(f"{len(left)} LoRA keys match no attention projection of this U-Net, e.g. {left[0]!r}")
-        ops.WEIGHT_EPOCH[0] += 1
+        ops.written_everywhere()
         return len(used) // 2
 
     def load_attn_procs(self, directory, weight_name="pytorch_lora_weights.safetensors"):

@@ -185,7 +185,7 @@ class EMAModel:
     def copy_to(self, parameters):
         for s, p in zip(self.shadow_params, list(parameters)):
             p.data.copy_(s.to(p.device).data)
-        ops.WEIGHT_EPOCH[0] += 1          # p.data.copy_ bumps no version counter: weight-derived caches must refresh
+        ops.written_everywhere()          # p.data.copy_ bumps no version counter: weight-derived caches must refresh
 
     def store(self, parameters):
         self.temp_stored_params = [p.detach().cpu().clone() for p in parameters]
@@ -196,7 +196,7 @@ class EMAModel:
         for c, p in zip(self.temp_stored_params, parameters):
             p.data.copy_(c.data)
         self.temp_stored_params = None
-        ops.WEIGHT_EPOCH[0] += 1
+        ops.written_everywhere()
 
     def to(self, device=None, dtype=None):
         self.shadow_params = [p.to(device=device, dtype=dtype) if p.is_floating_point() else p.to(device=device)
@@ -311,7 +311,7 @@ class FusedTrainer:
                     st["w"].copy_(loss_weights)
                 # derived weights (bf16 shadows of the LoRA buffer, ...) are refreshed by launches that key on the buffer's epoch: bump it so
                 # that the refresh is captured - a replay must re-derive them from the CURRENT weights
-                self.flat._gad_epoch = getattr(self.flat, "_gad_epoch", 0) + 1
+                ops.written(self.flat)
                 # scratch of the recorded launches: this graph's own (two trainers' graphs may replay on two streams at once)
                 st["ws"] = torch.empty(ops.WS_BYTES, dtype=torch.uint8, device=self.flat.device)
                 graph = torch.cuda.CUDAGraph()

@@ -447,21 +447,21 @@ def test_winograd_shadow_of_a_flat_buffer_follows_the_weights(ops):
             w.grad = None
 
     check_all()
-    U = flat._gad_wino4[1]                                                      # 32 x 32 maps: the F(4x4) form
-    assert ws[3]._gad_flat[1] not in flat._gad_wino4[2]                         # Cin = 3: not transformed
-    d0, dn = flat._gad_wino4[2][ws[1]._gad_flat[1]]
+    U = flat._gad_wino4.buffers[0]                                                      # 32 x 32 maps: the F(4x4) form
+    assert ws[3]._gad_flat[1] not in flat._gad_wino4.where                         # Cin = 3: not transformed
+    d0, dn = flat._gad_wino4.where[ws[1]._gad_flat[1]]
     G = torch.tensor([[1 / 4, 0, 0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6], [1 / 24, 1 / 12, 1 / 6], [1 / 24, -1 / 12, 1 / 6],
                       [0, 0, 1]], dtype=torch.float64)
     want = torch.einsum("ar,orsi,bs->aboi", G, ops.weight_krsc(ws[1]).detach().double().cpu(), G).reshape(36, 256, 128)
     close(U[d0:d0 + dn].view(36, 256, 128), want, rtol=1e-6, atol=1e-6)
     with torch.no_grad():
         flat.detach().mul_(1.5)
-    flat._gad_epoch = getattr(flat, "_gad_epoch", 0) + 1
+    ops.written(flat)
     check_all()
     with torch.no_grad():
         ws[2].copy_(ws[2] * 0.25)
     check_all()
-    assert flat._gad_wino4[1] is U
+    assert flat._gad_wino4.buffers[0] is U
 
 
 def test_conv_autograd_function(ops):
@@ -910,7 +910,7 @@ def test_conv_fwd_bf16_operands(ops, case, tile):
                                     residual=nhwc(res), tile_hint=tile)
         assert torch.equal(got_ng, got)
         if c["k"] == 3 and c["Cin"] % 32 == 0:
-            assert wg._gad_bf16[1].dtype == torch.bfloat16
+            assert wg._gad_bf16.value.dtype == torch.bfloat16
             wg.mul_(2.0)                                       # in-place change -> the cached copy is rebuilt
             got2 = ops.conv2d_fwd_raw(nhwc(x), wg, None, c["stride"], c["pad"], c["ups"], tile_hint=tile)
             ref2 = ops.conv2d_fwd_raw(nhwc(x), cl_weight(w * 2), None, c["stride"], c["pad"], c["ups"], tile_hint=tile)
@@ -1291,17 +1291,17 @@ def test_trainable_weights_in_a_flat_buffer_take_the_rotated_shadow(ops, prec):
             close(dx, dx_native, rtol=tol, atol=tol)
 
     check_all()
-    shadow = flat._gad_rot[1]
+    shadow = flat._gad_rot.buffers[0]
     got = shadow[ws[1]._gad_flat[1]:][:ws[1].numel()].view(96, 3, 3, 192)      # [ci][2-r][2-s][co]
     assert torch.equal(got, ops.weight_krsc(ws[1]).detach().flip(1, 2).permute(3, 1, 2, 0))
     with torch.no_grad():
         flat.detach().mul_(1.5)                                                 # what the raw optimizer kernel does ...
-    flat._gad_epoch = getattr(flat, "_gad_epoch", 0) + 1                        # ... and how it announces it
+    ops.written(flat)                                                           # ... and how it announces it
     check_all()
     with torch.no_grad():
         ws[2].copy_(ws[2] * 0.25)                                               # through torch: only ws[2]._version moves
     check_all()
-    assert flat._gad_rot[1] is shadow                                           # refreshed in place, one buffer
+    assert flat._gad_rot.buffers[0] is shadow                                           # refreshed in place, one buffer
 
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
