@@ -17,6 +17,7 @@ from .scoring import diversity_against_dataset, fid_against_dataset, global_scor
 from .sd import UNet2DConditionModel  # noqa: F401,E402
 from .local import LocalBehaviors, local_model_behaviors  # noqa: F401,E402
 from .influence import InfluenceUnlearner  # noqa: F401,E402
+from .lora import LoraConfig, get_peft_model, lora_parameters, merge_and_unload  # noqa: F401,E402
 from .similarity import cosine_rows, group_aggregate, write_baselines  # noqa: F401,E402
 from .vae import AutoencoderKL, VQModel  # noqa: F401,E402
 from .text import CLIPTextModel, CLIPTokenizer, TextTower  # noqa: F401,E402

@@ -103,6 +103,15 @@ class HGemmSegArgs(C.Structure):
                 ("splitk_hint", C.c_int32)]
 
 
+class LoraDropoutArgs(C.Structure):
+    """gad_lora_dropout_args (include/gad.h): dropout LoRA down-projection of up to four projections sharing their input"""
+    _fields_ = [("x", C.c_void_p), ("ldx", C.c_int64), ("M", C.c_int64), ("C", C.c_int32), ("r", C.c_int32),
+                ("n_proj", C.c_int32), ("layer", C.c_uint32), ("A", C.c_void_p * 4), ("mid", C.c_void_p * 4),
+                ("dmid", C.c_void_p * 4), ("dA", C.c_void_p * 4), ("dx", C.c_void_p), ("ld_dx", C.c_int64), ("p", C.c_double),
+                ("scale", C.c_float), ("seed", C.c_uint32), ("offset", C.c_uint32), ("max_blocks", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 JL_NORMAL, JL_RADEMACHER = 0, 1
 POOL_MAX, POOL_AVG, POOL_AVG_VALID = 0, 1, 2
 GELU_ERF, GELU_QUICK = 0, 1
@@ -204,6 +213,11 @@ SIGNATURES = {
     "gad_wf_dots_workspace_bytes": (_i64, [_i64]),
     "gad_wf_dots": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "gad_wf_update": (C.c_int, [_vp, _vp, _vp, _f64, _i64, _vp]),
+    # LoRA unlearning: dropout down-projection and merge (csrc/lora.hip)
+    "gad_lora_down_dropout_workspace_bytes": (_i64, [C.POINTER(LoraDropoutArgs)]),
+    "gad_lora_down_dropout_fwd": (C.c_int, [C.POINTER(LoraDropoutArgs), _vp]),
+    "gad_lora_down_dropout_bwd": (C.c_int, [C.POINTER(LoraDropoutArgs), _vp]),
+    "gad_lora_merge": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _f32, _vp]),
     # score tail (csrc/scorenet.hip)
     "gad_pool2d": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "gad_resize_bilinear": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _vp]),

@@ -202,6 +202,11 @@ class Attention(nn.Module):
         h, x = self.group_norm.with_bypass(x)                        # :1297-1298 (NHWC: no transposes needed); x: alias for the residual
         res = x.view(b, hh * ww, c)
         h = h.view(b, hh * ww, c)
+        lq = getattr(self, "lora_qkv", None)
+        if lq is not None:             # peft-style LoRA with dropout on to_q / to_k / to_v (gad/lora.py): one node for the three
+            q, k, v = lq(self, h)
+            o = ops.attention_core(q, k, v, self.heads)
+            return self.to_out[0](o, residual=res, scale=scale).view(b, hh, ww, c)
         lora = any(l.lora_layer is not None for l in (self.to_q, self.to_k, self.to_v, self.to_out[0]))
         padded = self.dpad != self.dim_head and not lora
         sm_scale = self.dim_head ** -0.5 if padded else None         # the softmax scale of the TRUE head dim (:1321-1323)

@@ -1741,6 +1741,130 @@ def wf_update_raw(o, k, dots, N: float):
     check(_capi.load().gad_wf_update(o.data_ptr(), k.data_ptr(), dots.data_ptr(), float(N), o.numel(), _stream()), "gad_wf_update")
 
 
+def _lora_dropout_args(x2, downs, p, scale, seed, offset, layer, max_blocks=0):
+    """gad_lora_dropout_args over tokens x2 [M, C] and the contiguous down matrices [r, C] of the projections that share them,
+    with the stream's workspace (csrc/lora.hip)"""
+    M, Cc = x2.shape
+    a = _capi.LoraDropoutArgs()
+    a.x, a.ldx, a.M, a.C = _req_rows(x2, "lora x").data_ptr(), (x2.stride(0) if M > 1 else Cc), M, Cc
+    a.r, a.n_proj, a.layer = downs[0].shape[0], len(downs), layer
+    for j, d in enumerate(downs):
+        a.A[j] = _req(d, "lora down").data_ptr()
+    a.p, a.scale, a.seed, a.offset, a.max_blocks = float(p), float(scale), seed & 0xFFFFFFFF, offset & 0xFFFFFFFF, max_blocks
+    ws = workspace(x2.device)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    return a
+
+
+def _req_rows(t, name):
+    if not (t.is_cuda and t.dtype == torch.float32 and t.ndim == 2 and t.stride(1) == 1):
+        raise _capi.GadError(f"{name}: expected an fp32 device matrix with contiguous rows, got {t.dtype} {t.device} strides {t.stride()}")
+    return t
+
+
+def lora_down_dropout_fwd_raw(x2, downs, p, scale, seed, offset, layer, max_blocks=0):
+    """mid_j = scale * (x o m_j / (1 - p)) A_j^T for every projection j from one read of x -> [mid_j [M, r]]"""
+    a = _lora_dropout_args(x2, downs, p, scale, seed, offset, layer, max_blocks)
+    mids = [torch.empty((x2.shape[0], a.r), device=x2.device, dtype=torch.float32) for _ in downs]
+    for j, m in enumerate(mids):
+        a.mid[j] = m.data_ptr()
+    check(_capi.load().gad_lora_down_dropout_fwd(C.byref(a), _stream()), "gad_lora_down_dropout_fwd")
+    return mids
+
+
+def lora_down_dropout_bwd_raw(x2, downs, dmids, dx2, p, seed, offset, layer, outs=None):
+    """dA_j = dmid_j^T (x o m_j / (1 - p)) -> [dA_j [r, C]] (into `outs[j]` where given), and dx2 += sum_j (dmid_j A_j) o m_j / (1 - p)
+    in place, with the forward's masks"""
+    a = _lora_dropout_args(x2, downs, p, 1.0, seed, offset, layer)
+    outs = list(outs) if outs is not None else [None] * len(downs)
+    for j, d in enumerate(downs):
+        if outs[j] is None:
+            outs[j] = torch.empty_like(d)
+        a.dmid[j], a.dA[j] = _req(dmids[j], "lora dmid").data_ptr(), _req(outs[j], "lora dA").data_ptr()
+    a.dx, a.ld_dx = _req_rows(dx2, "lora dx").data_ptr(), (dx2.stride(0) if dx2.shape[0] > 1 else dx2.shape[1])
+    check(_capi.load().gad_lora_down_dropout_bwd(C.byref(a), _stream()), "gad_lora_down_dropout_bwd")
+    return outs
+
+
+def lora_merge_raw(w, up, down, alpha):
+    """w [N, K] += alpha * up [N, r] @ down [r, K] in place (merge_and_unload; -alpha unmerges)"""
+    N, K = w.shape
+    check(_capi.load().gad_lora_merge(_req_rows(w, "lora merge W").data_ptr(), w.stride(0) if N > 1 else K, _req(up, "lora up").data_ptr(),
+                                      _req(down, "lora down").data_ptr(), N, K, up.shape[1], float(alpha), _stream()), "gad_lora_merge")
+    written_everywhere()        # a device-pointer write: whatever is derived from w must refresh
+
+
+class LoraDropoutQKVFn(torch.autograd.Function):
+    """The three LoRA projections of one attention block as ONE autograd node (peft: y_j = x W_j^T + b_j + s (drop_j(x) A_j^T) B_j^T,
+    each projection with its own dropout mask; reference unconditional_generation/unlearn.py:410-416).
+    Forward:  gad_lora_down_dropout_fwd once (x read once, masks regenerated, never stored), then per projection the
+              K-concatenated launch over [x | mid_j] . [W_j | B_j]^T (base + side GEMM where the shapes rule that out).
+    Backward: dmid_j = s dy_j B_j and dB_j = dy_j^T mid_j (small GEMMs), the base data gradient sum_j dy_j W_j (each launch adds
+              onto the previous one in its epilogue), then gad_lora_down_dropout_bwd for dA_j and the LoRA part of dx.
+    The base weights are frozen (get_peft_model): no dW / db is formed."""
+
+    @staticmethod
+    def forward(ctx, x, ws_, bs_, meta, *ab):
+        n = len(ws_)
+        downs, ups = ab[:n], ab[n:]
+        p, s, seed, offset, layer = meta
+        shp = x.shape
+        x2 = _req(x, "lora qkv x").view(-1, shp[-1])
+        M, K = x2.shape
+        r = downs[0].shape[0]
+        mids = lora_down_dropout_fwd_raw(x2, [d.detach() for d in downs], p, s, seed, offset, layer)
+        ys = []
+        for w, b, up, mid in zip(ws_, bs_, ups, mids):
+            N = w.shape[0]
+            y = torch.empty((M, N), device=x.device, dtype=torch.float32)
+            if lora_fusable(K, N, r):
+                gemm_raw(x2, w, y, A_KC, B_KC, M, N, K + r, K, K, N, bias=b, A_k2=mid, B_k2=up, k_split=K)
+            else:
+                base = linear_fwd_raw(x2, w, b)
+                gemm_raw(mid, up, y, A_KC, B_KC, M, N, r, r, r, N, residual=base, ldr=N)
+            ys.append(y.view(*shp[:-1], N))
+        ctx.save_for_backward(x2, *downs, *ups, *mids)
+        ctx.frozen, ctx.meta, ctx.shp, ctx.n = (ws_, bs_), meta, shp, n
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *dys):
+        n = ctx.n
+        saved = ctx.saved_tensors
+        x2, downs, ups, mids = saved[0], saved[1:1 + n], saved[1 + n:1 + 2 * n], saved[1 + 2 * n:]
+        ws_, _ = ctx.frozen
+        p, s, seed, offset, layer = ctx.meta
+        M, K = x2.shape
+        r = downs[0].shape[0]
+        dx = torch.empty((M, K), device=x2.device, dtype=torch.float32)
+        dmids, d_ups = [], []
+        for j, (w, up, mid) in enumerate(zip(ws_, ups, mids)):
+            N = w.shape[0]
+            dy2 = dys[j].contiguous().view(-1, N)
+            dmid = torch.empty((M, r), device=x2.device, dtype=torch.float32)
+            gemm_raw(dy2, up, dmid, A_KC, B_MC, M, r, N, N, r, r, alpha=s)                         # s dy B
+            dmids.append(dmid)
+            d_ups.append(_param_grad(up, lambda o, dy2=dy2, mid=mid: linear_wgrad_raw(dy2, mid, out=o)))   # dy^T mid
+            gemm_raw(dy2, w, dx, A_KC, B_MC, M, K, N, N, K, K, residual=dx if j else None, ldr=K if j else 0)   # dx (+)= dy W
+        sinks = [_sink(d) for d in downs]
+        outs = [v if (v is not None and first) else None for v, first in sinks]
+        dAs = lora_down_dropout_bwd_raw(x2, [d.detach() for d in downs], dmids, dx, p, seed, offset, layer, outs=outs)
+        d_downs = []
+        for (v, first), g in zip(sinks, dAs):
+            if v is None:
+                d_downs.append(g)
+            else:
+                if not first:
+                    v.add_(g)
+                d_downs.append(None)
+        return (dx.view(ctx.shp) if ctx.needs_input_grad[0] else None, None, None, None, *d_downs, *d_ups)
+
+
+def lora_dropout_qkv(x, ws_, bs_, downs, ups, p, s, seed, offset, layer):
+    """(q, k, v) of an attention block under LoRA with dropout; `ws_` / `bs_` the frozen base weights and biases"""
+    return LoraDropoutQKVFn.apply(x, tuple(ws_), tuple(bs_), (float(p), float(s), int(seed), int(offset), int(layer)), *downs, *ups)
+
+
 # ----------------------------------------------------------------------------------
 # transformer-block operators (UNet2DConditionModel)
 # ----------------------------------------------------------------------------------

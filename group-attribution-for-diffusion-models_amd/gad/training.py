@@ -228,11 +228,15 @@ class FusedTrainer:
     the caller (so the RNG policy stays in the entry point)."""
 
     def __init__(self, model, scheduler, ema: EMAModel | None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
-                 weight_decay=0.0, adamw=False, max_grad_norm=1.0, loss_sign=1.0, params=None, lr_schedule=None, use_graph=False):
+                 weight_decay=0.0, adamw=False, max_grad_norm=1.0, loss_sign=1.0, params=None, lr_schedule=None, use_graph=False,
+                 groups=None):
         """`use_graph`: capture add_noise -> forward -> loss -> backward of one step into a hipGraph after `GRAPH_WARMUP` eager steps and
         replay it from then on (the optimizer launch stays eager: its step count and learning rate are host scalars).  For steps that are
         launch-bound on the host - the half-precision SD LoRA step issues ~2 900 short launches - : the same kernels in the same order,
-        bit-identical results, no per-launch host work.  Shapes must not change between steps; a capture that fails falls back to eager."""
+        bit-identical results, no per-launch host work.  Shapes must not change between steps; a capture that fails falls back to eager.
+        `groups`: [(slice of the flat buffer, lr multiplier)] - the optimizer runs once per slice at lr * multiplier under ONE clip norm
+        over the whole gradient buffer (LoRA+: peft's create_loraplus_optimizer, gad.lora_parameters); slices start on SLOT boundaries.
+        Without it: one launch over the whole buffer, as before."""
         self.model, self.scheduler, self.ema = model, scheduler, ema
         self.use_graph, self._graph, self._graph_failed = use_graph, None, False
         if params is None:                      # train everything (DDPM); else only `params` (LoRA: base frozen)
@@ -244,6 +248,13 @@ class FusedTrainer:
             self.params = list(params)
             self.flat, self.gflat = flatten_params(self.params)
         self.base_lr, self.lr_schedule = lr, lr_schedule
+        self.groups = [(sl, float(mult)) for sl, mult in groups] if groups else None
+        if self.groups:
+            if ema is not None:
+                raise ValueError("FusedTrainer: parameter groups are not combined with a fused EMA")
+            for sl, _ in self.groups:
+                if sl.start % SLOT or sl.stop % SLOT or not 0 <= sl.start < sl.stop <= self.flat.numel() or sl.step not in (None, 1):
+                    raise ValueError(f"FusedTrainer: group {sl} is not a run of whole slots of the flat buffer ({self.flat.numel()} floats)")
         self._sinks_checked, self._unwritten = False, []
         self.m = torch.zeros_like(self.flat)
         self.v = torch.zeros_like(self.flat)
@@ -352,6 +363,12 @@ class FusedTrainer:
         decay = self.ema.next_decay() if self.ema is not None else 0.0
         if self.lr_schedule is not None:        # LambdaLR semantics: step k (0-based) runs at base_lr * f(k)
             self.hp["lr"] = self.base_lr * self.lr_schedule(self.step_count - 1)
+        if self.groups:                         # one clip norm over every gradient, one launch per learning rate
+            for sl, mult in self.groups:
+                ops.clip_adam_ema_raw(self.flat[sl], self.gflat[sl], self.m[sl], self.v[sl], None, sumsq, max_norm=self.max_grad_norm or 0.0,
+                                      step=self.step_count, ema_decay=0.0, **{**self.hp, "lr": self.hp["lr"] * mult})
+            ops.written(self.flat)              # (the launches stamped their slice views: the residents key on the whole buffer's epoch)
+            return
         ops.clip_adam_ema_raw(self.flat, self.gflat, self.m, self.v, self.ema_flat, sumsq,
                               max_norm=self.max_grad_norm or 0.0, step=self.step_count, ema_decay=decay, **self.hp)
 

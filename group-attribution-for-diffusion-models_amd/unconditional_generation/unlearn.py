@@ -3,8 +3,9 @@ model-behaviour score - global (FID / IS / precision / recall, `--model_behavior
 MSE / NRMSE / SSIM against the full model's image and the diffusion loss, `--model_behavior local`) - and one jsonl row.
 
 Entry point kept from the reference (unconditional_generation/unlearn.py): same flags for the sFT path
-(`--method gd` / `ga`) and for influence unlearning (`--method iu`, `--iu_ratio`: :509-546 through
-`gad.InfluenceUnlearner`), same coalition semantics (the by_class quirk of :331 included), same jsonl keys
+(`--method gd` / `ga`), for influence unlearning (`--method iu`, `--iu_ratio`: :509-546 through
+`gad.InfluenceUnlearner`) and for LoRA unlearning (`--method lora` / `lora_u`, `--lora_rank`, `--lora_dropout`: :404-424,
+629-634, 748-749 through `gad.get_peft_model` / `gad.merge_and_unload`), same coalition semantics (the by_class quirk of :331 included), same jsonl keys
 (:277,834-837,960-968).  The cycle itself is `gad.coalition.CoalitionEngine`: fused training steps,
 EMA weights, 64-image preview, fused-batch DDIM sampling and the Frechet score on the MI355X.
 """
@@ -130,12 +131,65 @@ def influence_unlearn(args, backend, config, dataset, model, ema_model, schedule
     return len(remaining)
 
 
+LORA_ALPHA, LORAPLUS_LR_RATIO = 32, 16          # fixed by the reference whatever the rank (:413, :423)
+
+
+def lora_unlearn(args, backend, config, dataset, model, ema_model, scheduler, remaining_idx):
+    """LoRA unlearning (:404-424, 548-642, 748-749): the gd loop body over the LoRA matrices of to_q / to_k / to_v alone (base frozen),
+    LoRA+ Adam (B at 16 x the A matrices' rate, one clip norm over all of them), then ONE merge.
+    The reference merges a deep copy of the model after every step and hands it to `ema_model.step`; every merged parameter is
+    frozen, so that step copies instead of averaging and the shadows are the merged weights of the last step.  Here: merge once
+    after the loop, copy into the shadows and advance the EMA's step counter by the steps taken - the same end state without
+    streaming the whole model per step.  -> the model with the LoRA layers merged and removed"""
+    device = args.device
+    model = backend.get_peft_model(model, backend.LoraConfig(r=args.lora_rank, target_modules=["to_q", "to_v", "to_k"],
+                                                               lora_alpha=LORA_ALPHA, lora_dropout=args.lora_dropout))
+    params, groups = backend.lora_parameters(model, LORAPLUS_LR_RATIO)
+    # create_loraplus_optimizer passes lr alone: Adam's defaults, no weight decay
+    trainer = backend.FusedTrainer(model, scheduler, None, lr=config["optimizer_config"]["kwargs"].get("lr", 1e-4), weight_decay=0.0,
+                                   adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0, params=params,
+                                   groups=groups)
+    loader = backend.DeviceLoader(dataset, remaining_idx, config["batch_size"], device)
+    n_t = scheduler.config.num_train_timesteps
+    model.train()
+    steps = 0
+    while steps < args.gd_steps:
+        for image, _ in loader:
+            noise = torch.randn_like(image)
+            ts = backend.antithetic_timesteps(n_t, image.shape[0], device)
+            trainer.step(image, noise, ts)
+            steps += 1
+            if steps == args.gd_steps:
+                break
+    model = backend.merge_and_unload(model)
+    with torch.no_grad():
+        for s, p in zip(ema_model.shadow_params, model.parameters()):
+            s.copy_(p.detach())
+    ema_model.optimization_step += steps
+    ema_model.cur_decay_value = ema_model.get_decay(ema_model.optimization_step)
+    return model
+
+
 def main(args, backend=None):
     if backend is None:
         import gad as backend
-    if args.method not in ("gd", "gd_u", "ga", "ga_u", "iu"):
-        raise NotImplementedError(f"method={args.method}: the engine implements the sFT family (gd/ga) and influence unlearning "
-                                  "(iu); esd / lora / retrain / prune_fine_tune are not unlearn.py methods here")
+    lora = args.method in ("lora", "lora_u")
+    if args.method not in ("gd", "gd_u", "ga", "ga_u", "iu", "lora", "lora_u"):
+        raise NotImplementedError(f"method={args.method}: the engine implements the sFT family (gd/ga), influence unlearning (iu) and "
+                                  "LoRA unlearning (lora); esd / retrain / prune_fine_tune are not unlearn.py methods here")
+    if lora:
+        if args.load is None:
+            raise NotImplementedError(f"method={args.method} without --load: LoRA unlearning from a fresh model is not implemented - like the "
+                                      "sFT family and influence unlearning it adapts a pre-trained (pruned) checkpoint; pass its directory")
+        if args.use_8bit_optimizer:
+            raise NotImplementedError("--use_8bit_optimizer: bitsandbytes' Adam8bit (reference :446) is not built here; LoRA unlearning "
+                                      "runs fp32 LoRA+ Adam")
+        if args.gradient_accumulation_steps != 1:
+            raise NotImplementedError(f"--gradient_accumulation_steps={args.gradient_accumulation_steps}: only 1 is implemented "
+                                      "(the reference's default)")
+        if args.dataset == "imagenette":
+            raise NotImplementedError("--dataset imagenette: the reference's unlearn.py leaves this branch dead (label_tokenizer and "
+                                      "text_encoder are undefined at :576-577); LoRA unlearning covers the unconditional U-Nets")
     if hasattr(backend, "set_operand_precision"):      # --mixed_precision fp16|bf16 -> bf16 operands, fp32 everything else
         backend.set_operand_precision(args.mixed_precision)
     device = torch.device(args.device)
@@ -155,6 +209,10 @@ def main(args, backend=None):
     if args.method == "iu":
         t0 = time.time()
         steps_goal = influence_unlearn(args, backend, config, dataset, model, ema_model, scheduler, remaining_idx, removed_idx)
+    elif lora:
+        t0 = time.time()
+        steps_goal = args.gd_steps
+        model = lora_unlearn(args, backend, config, dataset, model, ema_model, scheduler, remaining_idx)
     else:
         okw = dict(config["optimizer_config"]["kwargs"])
         trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),

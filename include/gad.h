@@ -610,6 +610,56 @@ int gad_wf_dots(const float* o, const float* k, const float* g, int64_t n, doubl
 int gad_wf_update(float* o, float* k, const double* dots, double N, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * LoRA unlearning of the unconditional U-Nets (csrc/lora.hip; reference unconditional_generation/unlearn.py:404-424 through
+ * peft's LoRA layer, y = base(x) + B(A(dropout(x))) * alpha / r).  Up to four projections share the tokens x (an attention
+ * block's to_q / to_k / to_v, each with its own dropout mask):
+ *   gad_lora_down_dropout_fwd   mid_j [M][r] = scale * ( x o m_j / (1 - p) ) A_j^T                j < n_proj
+ *   gad_lora_down_dropout_bwd   dA_j  [r][C] = dmid_j^T ( x o m_j / (1 - p) )                      (overwritten)
+ *                               dx    [M][ld_dx] += sum_j ( dmid_j A_j ) o m_j / (1 - p)           (accumulated in place)
+ * mid_j feed the K-concatenated gad_gemm launch (A_k2 = mid_j, B_k2 = B_j); dmid_j = scale * dy_j B_j comes from gad_gemm.
+ * The keep mask m_j is never stored: m_j(m, c) is Philox-4x32-10 (Random123 constants) with key (seed, offset) and counter
+ * (c >> 2, m low 32 bits, m high 32 bits, (layer << 2) | j); channel c takes word c & 3 of the result and is kept when
+ * word >= floor(p * 2^32).  `offset` is the caller's step counter, `layer` (< 2^30) tells the attention blocks apart.  The
+ * result does not depend on the grid (max_blocks caps the forward's, 0 = default) or on which access path runs.
+ * p == 0 never calls Philox: the forward is then n_proj plain gad_gemm launches (alpha = scale), bit-equal to the plain
+ * down-projection.  No atomics: the dA partials of the row slabs (a plan that depends on M alone) are written to the
+ * workspace and added in slab order, so two launches give equal bits.  r a multiple of 4 in 4..64 (zero-padded to the
+ * MFMA's 16 in registers); A_j and dA_j contiguous [r][C], mid_j and dmid_j contiguous [M][r]; C % 4 == 0, strides that are
+ * multiples of 4 and 16-byte aligned pointers take float4 accesses, anything else guarded scalar ones.  Refused with a
+ * named error before any HIP call: p outside [0, 1), n_proj outside 1..4, a short workspace, a null pointer.
+ * workspace_bytes >= gad_lora_down_dropout_workspace_bytes(args) (-1 and gad_last_error() if the arguments are refused)
+ * serves both directions.
+ * gad_lora_merge: W[n][k] += alpha * sum_r B[n][r] A[r][k] in place (W row stride ldw; B [N][r], A [r][K] contiguous):
+ * merge_and_unload with alpha = lora_alpha / r, the inverse with -alpha.
+ * ---------------------------------------------------------------------------- */
+typedef struct gad_lora_dropout_args {
+  const float* x;           /* [M][ldx] tokens                                                */
+  int64_t ldx;
+  int64_t M;
+  int32_t C;                /* channels of x (the projections' in_features)                   */
+  int32_t r;                /* LoRA rank                                                      */
+  int32_t n_proj;           /* 1..4 projections sharing x                                     */
+  uint32_t layer;           /* mask stream of this attention block                            */
+  const float* A[4];        /* down matrices [r][C]                                           */
+  float* mid[4];            /* forward output [M][r]                                          */
+  const float* dmid[4];     /* backward input [M][r]                                          */
+  float* dA[4];             /* backward output [r][C]                                         */
+  float* dx;                /* backward: [M][ld_dx], accumulated onto                         */
+  int64_t ld_dx;
+  double p;                 /* dropout probability in [0, 1)                                  */
+  float scale;              /* forward: lora_alpha / r                                        */
+  uint32_t seed, offset;    /* Philox key                                                     */
+  int32_t max_blocks;       /* forward grid cap (0 = default)                                 */
+  void* workspace;
+  int64_t workspace_bytes;
+} gad_lora_dropout_args;
+
+int64_t gad_lora_down_dropout_workspace_bytes(const gad_lora_dropout_args* a);
+int gad_lora_down_dropout_fwd(const gad_lora_dropout_args* a, void* stream);
+int gad_lora_down_dropout_bwd(const gad_lora_dropout_args* a, void* stream);
+int gad_lora_merge(float* W, int64_t ldw, const float* B, const float* A, int32_t N, int32_t K, int32_t r, float alpha, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Score tail: the kernels between the convolutions of InceptionV3 (csrc/scorenet.hip, gad/inception.py; reference
  * src/attributions/global_scores/fid_score.py:23-107 and inception_score.py through pytorch-fid's InceptionV3, whose
  * F.max_pool2d / F.avg_pool2d / F.interpolate / F.relu these replace).  fp32 NHWC, bandwidth-bound, 64-bit element
