@@ -9,7 +9,12 @@ mkdir -p "$HERE/build"
 pids=()
 for f in gemm_f32 wino4_fused attention norm elementwise optim transformer half projector local scorenet influence manifold vit similarity vae text lora; do
   src="$HERE/csrc/$f.hip"; obj="$HERE/build/$f.o"
-  if [ ! -f "$obj" ] || [ "$src" -nt "$obj" ] || [ "$HERE/csrc/gad_common.h" -nt "$obj" ] || [ "$HERE/csrc/gad_reduce.h" -nt "$obj" ] || [ "$HERE/../include/gad.h" -nt "$obj" ] || [ "$HERE/csrc/gemm_dev.h" -nt "$obj" ]; then
+  stale=0
+  [ -f "$obj" ] || stale=1
+  for dep in "$src" "$HERE"/csrc/*.h "$HERE/../include/gad.h"; do   # every header: a new one cannot be forgotten
+    if [ "$dep" -nt "$obj" ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then
     extra=""
     # attention.hip: MFMA results feed the vector ALUs directly (softmax, dS), so keep them in VGPRs: with the default AGPR
     # form hipcc moved every score / gradient tile through v_accvgpr_read / _write (50-150 instructions per K/V tile)

@@ -30,26 +30,12 @@
 //
 // Any head dim <= 256 and any alignment: launches that cannot stream 16-byte pieces (the pruned CelebA model's d = 23 in
 // 322-float rows) run the `RG` instances of the same kernels - dword staging through registers, masks at d.
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int NT = 256;     // threads per workgroup (4 waves)
 constexpr int KV = 32;      // streamed rows per LDS tile
-
-__device__ __attribute__((aligned(64))) float g_attn_zero[16];
-
-__device__ __forceinline__ void glds16(const float* src, float* dst_wave_uniform) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)dst_wave_uniform, 16, 0, 0);
-}
-// publish LDS-DMA'd tiles: the DMA is a VMEM operation -> explicit vmcnt(0) before the barrier
-__device__ __forceinline__ void barrier_after_dma() {
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
-}
 
 template <int D>
 struct Cfg {
@@ -89,7 +75,7 @@ __device__ __forceinline__ void stage_tile(float* tile, const float* base, int l
       const int f = (piece * 64 + lane) * 4;
       const int row = f / C::S, col = f - row * C::S;
       const bool ok = row < KV && row0 + row < T && col < D;
-      const float* src = ok ? base + (long)(row0 + row) * ld + col : (const float*)g_attn_zero;
+      const float* src = ok ? base + (long)(row0 + row) * ld + col : g_zero_block.f32;
       glds16(src, tile + piece * 256);
     }
   }
@@ -130,7 +116,7 @@ __device__ __forceinline__ void stage_tile_lean(float* tile, const float* base, 
   for (int i = 0; i < TilePlan<D>::NP; ++i) {
     const int piece = wave + 4 * i;
     if (piece < C::NPIECE) {
-      const float* src = plan.off[i] >= 0 ? rowbase + plan.off[i] : (const float*)g_attn_zero;
+      const float* src = plan.off[i] >= 0 ? rowbase + plan.off[i] : g_zero_block.f32;
       glds16(src, tile + piece * 256);
     }
   }
@@ -273,7 +259,6 @@ __device__ __forceinline__ void row_frag_global(const float* base, int ld, int r
   }
 }
 
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float xmax16_32(float v) {        // max over the 4 lanes {l, l^16, l^32, l^48}
   v = fmaxf(v, __shfl_xor(v, 16, 64));
@@ -473,8 +458,8 @@ __global__ __launch_bounds__(NTW) void attn_fwd_wide_f32_kernel(const AttnDev p)
         const int f = (piece * 64 + lane) * 4;
         const int r = f / C::S;
         const bool okk = koff[i] >= 0 && (whole || row0 + r < p.Tk);
-        glds16(okk ? K + (long)row0 * p.ldk + koff[i] : (const float*)g_attn_zero, buf + piece * 256);
-        glds16(okk ? V + (long)row0 * p.ldv + voff[i] : (const float*)g_attn_zero, buf + C::TILE + piece * 256);
+        glds16(okk ? K + (long)row0 * p.ldk + koff[i] : g_zero_block.f32, buf + piece * 256);
+        glds16(okk ? V + (long)row0 * p.ldv + voff[i] : g_zero_block.f32, buf + C::TILE + piece * 256);
       }
     }
   };
@@ -499,8 +484,7 @@ __global__ __launch_bounds__(NTW) void attn_fwd_wide_f32_kernel(const AttnDev p)
     float* mine = xch + ((dh * 4 + w4) * 64 + lane) * 8;
     *reinterpret_cast<f32x4*>(mine) = s[0];
     *reinterpret_cast<f32x4*>(mine + 4) = s[1];
-    __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0) only: the next tile's LDS-DMA stays in flight across this barrier
-    __builtin_amdgcn_s_barrier();
+    barrier_lgkm0();                               // the next tile's LDS-DMA stays in flight across this barrier
     {
       const float* h0 = xch + ((0 * 4 + w4) * 64 + lane) * 8;
       const float* h1 = xch + ((1 * 4 + w4) * 64 + lane) * 8;
@@ -617,8 +601,8 @@ __global__ __launch_bounds__(NTW) void attn_fwd_d512_f32_kernel(const AttnDev p)
         const int f = (piece * 64 + lane) * 4;
         const int r = f / C::S;
         const bool okk = koff[i] >= 0 && (whole || row0 + r < p.Tk);
-        glds16(okk ? K + (long)row0 * p.ldk + koff[i] : (const float*)g_attn_zero, buf + piece * 256);
-        glds16(okk ? V + (long)row0 * p.ldv + voff[i] : (const float*)g_attn_zero, buf + C5::TILE + piece * 256);
+        glds16(okk ? K + (long)row0 * p.ldk + koff[i] : g_zero_block.f32, buf + piece * 256);
+        glds16(okk ? V + (long)row0 * p.ldv + voff[i] : g_zero_block.f32, buf + C5::TILE + piece * 256);
       }
     }
   };
@@ -648,8 +632,7 @@ __global__ __launch_bounds__(NTW) void attn_fwd_d512_f32_kernel(const AttnDev p)
       s = sa + sb;
     }
     *reinterpret_cast<f32x4*>(xch + ((dh * 4 + w4) * 64 + lane) * 4) = s;
-    __builtin_amdgcn_s_waitcnt(0xC07F);            // lgkmcnt(0) only: the next tile's LDS-DMA stays in flight across this barrier
-    __builtin_amdgcn_s_barrier();
+    barrier_lgkm0();                               // the next tile's LDS-DMA stays in flight across this barrier
     s = *reinterpret_cast<const f32x4*>(xch + ((0 * 4 + w4) * 64 + lane) * 4) +
         *reinterpret_cast<const f32x4*>(xch + ((1 * 4 + w4) * 64 + lane) * 4);
     if ((it + 1) * KV5 > p.Tk) {
@@ -1197,11 +1180,6 @@ __global__ void attn_dq_reduce_kernel(const AttnDev p, int nslab, int vec) {
 //     eight probabilities a lane holds are packed to bf16 in place and ARE the B operand; the A operand is read with
 //     the same row assignment.
 // ==================================================================================================================
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-
 template <int D>
 struct CfgH {
   static_assert(D % 8 == 0, "head dim must be a multiple of 8");
@@ -1215,7 +1193,7 @@ struct CfgH {
   static constexpr int SLOTS = (NF4 + NT - 1) / NT;        // per thread
 };
 
-__device__ __forceinline__ f32x4 mfma16h(bf16x8_t a, bf16x8_t b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma16h(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 // storage type of q / k / v / o and their gradients: fp32 (operand_precision = 1 of gad_attention_*) or bf16 (gad_h_attention_*:
 // the half-precision activation path, strides in elements)
@@ -1229,8 +1207,8 @@ __device__ __forceinline__ f32x4 load4(const unsigned short* p) {
 }
 __device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 __device__ __forceinline__ void store4(unsigned short* p, f32x4 v) {
-  const bf16x4_t h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-  *reinterpret_cast<bf16x4_t*>(p) = h;
+  const bf16x4 h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+  *reinterpret_cast<bf16x4*>(p) = h;
 }
 // issue the loads of rows row0 .. row0+KV-1 (zeros past T)
 template <int D, typename T>
@@ -1253,8 +1231,8 @@ __device__ __forceinline__ void tile_commit(unsigned short* img, const f32x4 (&r
     const int f = threadIdx.x + NT * i;
     if (f < C::NF4) {
       const int row = f / (D / 4), c4 = (f - row * (D / 4)) * 4;
-      const bf16x4_t h = {(__bf16)(r[i][0] * mul), (__bf16)(r[i][1] * mul), (__bf16)(r[i][2] * mul), (__bf16)(r[i][3] * mul)};
-      *reinterpret_cast<bf16x4_t*>(img + row * S + c4) = h;
+      const bf16x4 h = {(__bf16)(r[i][0] * mul), (__bf16)(r[i][1] * mul), (__bf16)(r[i][2] * mul), (__bf16)(r[i][3] * mul)};
+      *reinterpret_cast<bf16x4*>(img + row * S + c4) = h;
     }
   }
 }
@@ -1268,16 +1246,15 @@ struct TileIO {
 };
 template <int D>
 struct TileIO<D, true> {
-  typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
   static constexpr int N8 = KV * D / 8, SLOTS8 = (N8 + NT - 1) / NT;
-  u32x4_t r[SLOTS8];
+  u32x4 r[SLOTS8];
   __device__ __forceinline__ void fetch(const unsigned short* base, int ld, int row0, int T_) {
 #pragma unroll
     for (int i = 0; i < SLOTS8; ++i) {
       const int f = threadIdx.x + NT * i;
       const int row = f / (D / 8), c8 = (f - row * (D / 8)) * 8;
       const bool ok = f < N8 && row0 + row < T_;
-      r[i] = ok ? *reinterpret_cast<const u32x4_t*>(base + (long)(row0 + row) * ld + c8) : u32x4_t{0u, 0u, 0u, 0u};
+      r[i] = ok ? *reinterpret_cast<const u32x4*>(base + (long)(row0 + row) * ld + c8) : u32x4{0u, 0u, 0u, 0u};
     }
   }
   template <int S>
@@ -1288,31 +1265,31 @@ struct TileIO<D, true> {
       const int f = threadIdx.x + NT * i;
       if (f < N8) {
         const int row = f / (D / 8), c8 = (f - row * (D / 8)) * 8;
-        *reinterpret_cast<u32x4_t*>(img + row * S + c8) = r[i];
+        *reinterpret_cast<u32x4*>(img + row * S + c8) = r[i];
       }
     }
   }
 };
 // fragment whose lanes run along the image's rows: lane (row r0 + (l & 15), k group g = l >> 4) -> k = 32 s + 8 g + j
 template <int S>
-__device__ __forceinline__ bf16x8_t row_frag_h(const unsigned short* img, int r0, int s) {
+__device__ __forceinline__ bf16x8 row_frag_h(const unsigned short* img, int r0, int s) {
   const int lane = threadIdx.x & 63;
-  return *reinterpret_cast<const bf16x8_t*>(img + (r0 + (lane & 15)) * S + 32 * s + 8 * (lane >> 4));
+  return *reinterpret_cast<const bf16x8*>(img + (r0 + (lane & 15)) * S + 32 * s + 8 * (lane >> 4));
 }
 // fragment whose lanes run along the image's columns, contraction over 32 rows rb .. rb+31 with the slot assignment
 // (g, j < 4) -> row rb + 4 g + j, (g, j >= 4) -> row rb + 16 + 4 g + j - 4; lane l holds column c0 + (l & 15)
 template <int S>
-__device__ __forceinline__ bf16x8_t col_frag_h(const unsigned short* img, int rb, int c0) {
+__device__ __forceinline__ bf16x8 col_frag_h(const unsigned short* img, int rb, int c0) {
   const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
   const unsigned short* a0 = img + (rb + 4 * g + q) * S + c0 + 4 * pp;
-  const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)a0);
-  const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(a0 + 16 * S));
-  const s16x8_t both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, both);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 16 * S));
+  const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(bf16x8, both);
 }
 // loop-invariant row fragments straight from global memory (-> bf16, zero past the head dim / the sequence)
 template <int D, typename T>
-__device__ __forceinline__ void row_frag_global_h(const T* base, int ld, int row, bool ok, float mul, bf16x8_t (&f)[CfgH<D>::KS]) {
+__device__ __forceinline__ void row_frag_global_h(const T* base, int ld, int row, bool ok, float mul, bf16x8 (&f)[CfgH<D>::KS]) {
   using C = CfgH<D>;
   const int g = (threadIdx.x & 63) >> 4;
   const T* p = base + (long)(ok ? row : 0) * ld;
@@ -1322,12 +1299,12 @@ __device__ __forceinline__ void row_frag_global_h(const T* base, int ld, int row
     const bool in = ok && k < D;                      // D % 8 == 0: a group of 8 is all inside or all outside
     const f32x4 a = in ? load4(p + k) : f32x4{0.f, 0.f, 0.f, 0.f};
     const f32x4 b = in ? load4(p + k + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-    f[s] = bf16x8_t{(__bf16)(a[0] * mul), (__bf16)(a[1] * mul), (__bf16)(a[2] * mul), (__bf16)(a[3] * mul),
+    f[s] = bf16x8{(__bf16)(a[0] * mul), (__bf16)(a[1] * mul), (__bf16)(a[2] * mul), (__bf16)(a[3] * mul),
                     (__bf16)(b[0] * mul), (__bf16)(b[1] * mul), (__bf16)(b[2] * mul), (__bf16)(b[3] * mul)};
   }
 }
-__device__ __forceinline__ bf16x8_t pack8(const f32x4& a, const f32x4& b) {
-  return bf16x8_t{(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3], (__bf16)b[0], (__bf16)b[1], (__bf16)b[2], (__bf16)b[3]};
+__device__ __forceinline__ bf16x8 pack8(const f32x4& a, const f32x4& b) {
+  return bf16x8{(__bf16)a[0], (__bf16)a[1], (__bf16)a[2], (__bf16)a[3], (__bf16)b[0], (__bf16)b[1], (__bf16)b[2], (__bf16)b[3]};
 }
 __device__ __forceinline__ void zero_lds(unsigned short* lds, int n_elems) {
   for (int i = threadIdx.x * 8; i < n_elems; i += NT * 8) *reinterpret_cast<f32x4*>(lds + i) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1346,7 +1323,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_bf16_kernel(const AttnDev p) {
   const T* V = reinterpret_cast<const T*>(p.v) + b * p.sv + h * D;
   const int qw = blk * (64 * NQ) + wave * (16 * NQ);
 
-  bf16x8_t qf[NQ][C::KS];
+  bf16x8 qf[NQ][C::KS];
 #pragma unroll
   for (int t = 0; t < NQ; ++t) row_frag_global_h<D>(Q, p.ldq, qw + 16 * t + c, qw + 16 * t + c < p.Tq, p.scale * LOG2E, qf[t]);
   f32x4 o[C::NDV][NQ];
@@ -1383,7 +1360,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_bf16_kernel(const AttnDev p) {
       for (int t = 0; t < NQ; ++t) s[kt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int st = 0; st < C::KS; ++st) {
-        const bf16x8_t kf = row_frag_h<C::SK>(kimg, 16 * kt, st);
+        const bf16x8 kf = row_frag_h<C::SK>(kimg, 16 * kt, st);
 #pragma unroll
         for (int t = 0; t < NQ; ++t) s[kt][t] = mfma16h(kf, qf[t][st], s[kt][t]);
       }
@@ -1397,7 +1374,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_bf16_kernel(const AttnDev p) {
 #pragma unroll
             for (int t = 0; t < NQ; ++t) s[kt][t][e] = -__builtin_inff();
     }
-    bf16x8_t pb[NQ];
+    bf16x8 pb[NQ];
 #pragma unroll
     for (int t = 0; t < NQ; ++t) {
       float mx = fmaxf(fmaxf(fmaxf(s[0][t][0], s[0][t][1]), fmaxf(s[0][t][2], s[0][t][3])),
@@ -1422,7 +1399,7 @@ __global__ __launch_bounds__(NT) void attn_fwd_bf16_kernel(const AttnDev p) {
     }
 #pragma unroll
     for (int i = 0; i < C::NDV; ++i) {
-      const bf16x8_t vf = col_frag_h<C::SV>(vimg, 0, 16 * i);
+      const bf16x8 vf = col_frag_h<C::SV>(vimg, 0, 16 * i);
 #pragma unroll
       for (int t = 0; t < NQ; ++t) o[i][t] = mfma16h(vf, pb[t], o[i][t]);
     }
@@ -1468,7 +1445,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_bf16_kernel(const AttnDev p) {
   const T* V = reinterpret_cast<const T*>(p.v) + b * p.sv + h * D;
   int row[NU];
   bool rok[NU];
-  bf16x8_t qf[NU][C::KS], dof[NU][C::KS];
+  bf16x8 qf[NU][C::KS], dof[NU][C::KS];
   float L2[NU], dl[NU];
   f32x4 dq[NU][C::NDV];
 #pragma unroll
@@ -1503,7 +1480,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_bf16_kernel(const AttnDev p) {
     f32x4 ds[NU][2];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
-      bf16x8_t ka[C::KS], va[C::KS];
+      bf16x8 ka[C::KS], va[C::KS];
 #pragma unroll
       for (int st = 0; st < C::KS; ++st) { ka[st] = row_frag_h<C::SV>(kimg, 16 * kt, st); va[st] = row_frag_h<C::SV>(vimg, 16 * kt, st); }
 #pragma unroll
@@ -1522,12 +1499,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_dq_bf16_kernel(const AttnDev p) {
         }
       }
     }
-    bf16x8_t dsb[NU];
+    bf16x8 dsb[NU];
 #pragma unroll
     for (int u = 0; u < NU; ++u) dsb[u] = pack8(ds[u][0], ds[u][1]);
 #pragma unroll
     for (int i = 0; i < C::NDV; ++i) {
-      const bf16x8_t kc = col_frag_h<C::SV>(kimg, 0, 16 * i);
+      const bf16x8 kc = col_frag_h<C::SV>(kimg, 0, 16 * i);
 #pragma unroll
       for (int u = 0; u < NU; ++u) dq[u][i] = mfma16h(kc, dsb[u], dq[u][i]);
     }
@@ -1564,7 +1541,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_bf16_kernel(const AttnDev p) 
   const T* DO = reinterpret_cast<const T*>(p.d_o) + b * p.sdo + h * D;
   int key[NU];
   bool kok[NU];
-  bf16x8_t kf[NU][C::KS], vf[NU][C::KS];
+  bf16x8 kf[NU][C::KS], vf[NU][C::KS];
   f32x4 dk[NU][C::NDV], dv[NU][C::NDV];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
@@ -1617,7 +1594,7 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_bf16_kernel(const AttnDev p) 
     f32x4 pr[NU][2], ds[NU][2];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      bf16x8_t qa[C::KS], ga[C::KS];
+      bf16x8 qa[C::KS], ga[C::KS];
 #pragma unroll
       for (int st = 0; st < C::KS; ++st) { qa[st] = row_frag_h<C::SV>(qimg, 16 * t, st); ga[st] = row_frag_h<C::SV>(gimg, 16 * t, st); }
       float L2[4], dl[4];
@@ -1645,12 +1622,12 @@ __global__ __launch_bounds__(NT) void attn_bwd_dkv_bf16_kernel(const AttnDev p) 
         }
       }
     }
-    bf16x8_t pb[NU], dsb[NU];
+    bf16x8 pb[NU], dsb[NU];
 #pragma unroll
     for (int u = 0; u < NU; ++u) { pb[u] = pack8(pr[u][0], pr[u][1]); dsb[u] = pack8(ds[u][0], ds[u][1]); }
 #pragma unroll
     for (int i = 0; i < C::NDV; ++i) {
-      const bf16x8_t gc = col_frag_h<C::SV>(gimg, 0, 16 * i), qc = col_frag_h<C::SV>(qimg, 0, 16 * i);
+      const bf16x8 gc = col_frag_h<C::SV>(gimg, 0, 16 * i), qc = col_frag_h<C::SV>(qimg, 0, 16 * i);
 #pragma unroll
       for (int u = 0; u < NU; ++u) {
         dv[u][i] = mfma16h(gc, pb[u], dv[u][i]);
@@ -1714,8 +1691,8 @@ __global__ __launch_bounds__(NTC) void attn_causal_f32_kernel(const AttnDev p, c
     const int f = (piece * 64 + lane) * 4;
     const int row = f / C::S, col = f - row * C::S;
     const bool ok = row < T && col < D;
-    glds16(ok ? K + (long)row * p.ldk + col : (const float*)g_attn_zero, kimg + piece * 256);
-    glds16(ok ? V + (long)row * p.ldv + col : (const float*)g_attn_zero, vimg + piece * 256);
+    glds16(ok ? K + (long)row * p.ldk + col : g_zero_block.f32, kimg + piece * 256);
+    glds16(ok ? V + (long)row * p.ldv + col : g_zero_block.f32, vimg + piece * 256);
   }
   const int q0 = 16 * wave, row = q0 + c;
   float qf[C::KS];

@@ -4,7 +4,7 @@
 // are deterministic run to run (no float atomics).
 #include <stdarg.h>
 
-#include "gad_common.h"
+#include "gad_dev.h"
 #include "gad_reduce.h"
 
 // ------------------------------------------------------------------ error state ----
@@ -25,8 +25,6 @@ inline dim3 ew_grid(int64_t n_vec) {
   int64_t b = gad_ceil_div(n_vec > 0 ? n_vec : 1, NT);
   return dim3((unsigned)(b < 2048 ? b : 2048));
 }
-
-__device__ __forceinline__ float silu_f(float z) { return z / (1.f + expf(-z)); }
 
 // Generic elementwise launcher: F(i4 index, vectors) over n elements; requires 16-B aligned
 // pointers, handles n % 4 tail with the scalar functor.

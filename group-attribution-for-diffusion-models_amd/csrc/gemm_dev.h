@@ -1,32 +1,16 @@
-// Device-side building blocks shared by the contraction kernels of gemm_f32.hip and wino4_fused.hip (gfx950 only):
-// launch-argument struct, LDS-DMA staging, the XOR-swizzled KC tile image and its fragment reads, the XCD-aware block remap.
+// Device-side building blocks of the fp32 contraction kernels of gemm_f32.hip and wino4_fused.hip (gfx950 only):
+// launch-argument struct, tile slots and loaders, the XOR-swizzled KC tile image and its fragment reads, Winograd transforms.
+// The LDS-DMA issue, the waits and the zero block are gad_dev.h's.
 #pragma once
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace gadk {
 
 constexpr int BK = 32;
 constexpr int NTHREADS = 256;
 
-// 64 bytes of zeros in device memory: the DMA source of padding / out-of-range tile slots
-static __device__ __attribute__((aligned(64))) float g_zero_block[16];
-
 // physical float offset of logical 16-B chunk q (0..7) of KC-tile row r
 __device__ __forceinline__ int kc_off(int r, int q) { return r * BK + ((q ^ ((r >> 1) & 7)) << 2); }
-
-// LDS-DMA: 64 lanes x 16 B -> LDS [dst, dst + 1 KiB), lane-linear; src is per lane
-__device__ __forceinline__ void glds16(const float* src, float* dst_wave_uniform) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)dst_wave_uniform, 16, 0, 0);
-}
-
-// A barrier that publishes LDS-DMA'd tiles: the DMA is a VMEM operation (vmcnt), and the compiler's own waitcnt placement
-// at __syncthreads() only covers it when it happens to track the LDS side effect - so wait for it explicitly.
-// s_waitcnt immediate (gfx9): vmcnt = 0 (bits 3:0 and 15:14), expcnt = 7 (no wait), lgkmcnt = 15 (no wait).
-__device__ __forceinline__ void barrier_after_dma() {
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-  __syncthreads();
-}
 
 // division by a launch-invariant divisor: q = (mulhi(n, mul) + n) >> shift, exact for 0 <= n < 2^31
 struct FastDiv {
@@ -117,17 +101,8 @@ struct MCSlots {
 // branch-free source select: offsets are always computed (possibly from out-of-range coordinates), masked
 // to 0 when invalid and added to either the tensor base or the zero block
 __device__ __forceinline__ const float* sel_src(const float* base, long off, bool ok) {
-  const float* b = ok ? base : (const float*)g_zero_block;
+  const float* b = ok ? base : g_zero_block.f32;
   return b + (off & -(long)ok);
-}
-
-
-// Workgroup id -> work item, XCD-aware and bijective: hardware deals consecutive workgroup ids round-robin to the 8 XCDs
-// (each with its own L2); this hands every XCD a CONTIGUOUS range of work items, so tiles that share an operand panel
-// (neighbouring tile_n of one tile_m, the halo rows of neighbouring row tiles) meet in one L2.
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
 }
 
 constexpr int EPI_LD = 40;                       // scratch row stride in floats

@@ -31,7 +31,6 @@
 //   gemm_bf16_kernel            the generic engine with bf16 operands (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
 //   conv3x3_patch_bf16_kernel   the patch convolution with bf16 operands (optionally a bf16 weight copy by LDS-DMA)
 //   splitk_reduce_kernel        deterministic reduction + fused epilogue of any split launch
-#include "gad_common.h"
 #include "gemm_dev.h"
 
 using namespace gadk;
@@ -857,17 +856,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const DevArgs p) {
 // read with the transposing ds_read_b64_tr_b16.  All six operand pairs are instantiated; launches whose operands
 // cannot be read as aligned float4 (Cin = 3, Tk = 77 ...) stay on the fp32 kernel.
 // ------------------------------------------------------------------------------------
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 constexpr int LDK = BK + 8;
 // MC-type tiles [32 k][rows + pad]: the row stride in dwords is 16 (mod 64) (rows 128) or 48 (mod 64) (rows 64), so the
 // 4 k-rows x 16-dword segments one 32-lane half of a ds_read_b64_tr_b16 touches are 64 distinct banks
 template <int ROWS> struct LdmOf { static constexpr int v = ROWS == 128 ? 160 : 96; };
 
 __device__ __forceinline__ void store_bf16x4(unsigned short* dst, f32x4 v) {
-  bf16x4_t h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-  *reinterpret_cast<bf16x4_t*>(dst) = h;
+  bf16x4 h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+  *reinterpret_cast<bf16x4*>(dst) = h;
 }
 
 // bf16 tile of one operand: element count, where a thread's slot i goes, and the MFMA fragment of a 32-row
@@ -880,8 +876,8 @@ struct Bf16Tile<true, ROWS> {
   __device__ static void put(unsigned short* tile, int i, f32x4 v) {
     store_bf16x4(tile + KCSlots<ROWS>::row(i) * LDK + KCSlots<ROWS>::kq4(), v);
   }
-  __device__ static bf16x8_t frag(const unsigned short* tile, int r0, int ks, int lane) {
-    return *reinterpret_cast<const bf16x8_t*>(tile + (r0 + (lane & 31)) * LDK + ks * 16 + 8 * (lane >> 5));
+  __device__ static bf16x8 frag(const unsigned short* tile, int r0, int ks, int lane) {
+    return *reinterpret_cast<const bf16x8*>(tile + (r0 + (lane & 31)) * LDK + ks * 16 + 8 * (lane >> 5));
   }
 };
 template <int ROWS>
@@ -893,14 +889,13 @@ struct Bf16Tile<false, ROWS> {
   }
   // transposed read: per 16-lane group a 4(k) x 16(row) block; lane 4q+p supplies row q, columns 4p..4p+3 and
   // receives the 4 k-values of column (lane & 15)  (every lane must be active: EXEC all ones)
-  __device__ static bf16x8_t frag(const unsigned short* tile, int r0, int ks, int lane) {
+  __device__ static bf16x8 frag(const unsigned short* tile, int r0, int ks, int lane) {
     const int q = (lane & 15) >> 2, pp = lane & 3;
     const unsigned short* a0 = tile + (ks * 16 + 8 * (lane >> 5) + q) * LDM + r0 + 16 * ((lane >> 4) & 1) + 4 * pp;
-    s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)a0);
-    s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(a0 + 4 * LDM));
-    typedef short s16x8_t __attribute__((ext_vector_type(8)));
-    s16x8_t both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8_t, both);
+    s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a0);
+    s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a0 + 4 * LDM));
+    s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, both);
   }
 };
 
@@ -984,7 +979,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_bf16_kernel(const DevArgs p) {
     fetch((kt + 1 < nkt) ? k0_of(kt + 1) : p.K);   // past the end every slot reads zeros
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t fa[TM], fb[TN];
+      bf16x8 fa[TM], fb[TN];
 #pragma unroll
       for (int i = 0; i < TM; ++i) fa[i] = AT::frag(la, wm * (BM / 2) + i * 32, ks, lane);
 #pragma unroll
@@ -1090,15 +1085,14 @@ __global__ __launch_bounds__(NTHREADS, (W == 64 || NI == 8) ? 2 : 3) void conv3x
       const int row = j * 64 + wave * 16 + (lane >> 2);
       const int c = (lane & 3) ^ ((row >> 2) & 3);
       const bool ok = col0 + row < p.N && k0 < p.K;
-      const unsigned short* src = ok ? p.Bh + (long)(col0 + row) * p.ldb + k0 + c * 8 : (const unsigned short*)g_zero_block;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(tb + (j * 64 + wave * 16) * BK), 16, 0, 0);
+      const unsigned short* src = ok ? p.Bh + (long)(col0 + row) * p.ldb + k0 + c * 8 : g_zero_block.b16;
+      glds16(src, tb + (j * 64 + wave * 16) * BK);
     }
   };
-  auto frag_b = [&](const unsigned short* tb, int r0, int ks) -> bf16x8_t {
+  auto frag_b = [&](const unsigned short* tb, int r0, int ks) -> bf16x8 {
     if (!WB) return Bf16Tile<true, BN>::frag(tb, r0, ks, lane);
     const int row = r0 + l31;
-    return *reinterpret_cast<const bf16x8_t*>(tb + row * BK + (((2 * ks + h) ^ ((row >> 2) & 3)) << 3));
+    return *reinterpret_cast<const bf16x8*>(tb + row * BK + (((2 * ks + h) ^ ((row >> 2) & 3)) << 3));
   };
 
   f32x16 acc[TM][TN];
@@ -1154,9 +1148,9 @@ __global__ __launch_bounds__(NTHREADS, (W == 64 || NI == 8) ? 2 : 3) void conv3x
     const int tshift = (r * PW + s3) * LDK;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks) {
-      bf16x8_t fa[TM], fb[TN];
+      bf16x8 fa[TM], fb[TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8_t*>(pa + abase[i] + tshift + ks * 16);
+      for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(pa + abase[i] + tshift + ks * 16);
 #pragma unroll
       for (int j = 0; j < TN; ++j) fb[j] = frag_b(lb, wn * (BN / 2) + j * 32, ks);
 #pragma unroll
@@ -1601,7 +1595,6 @@ __global__ __launch_bounds__(NTHREADS) void conv3x3_fewout_kernel(const DevArgs 
     }
   };
 
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
   f32x2 acc[NOUT];
 #pragma unroll
   for (int n = 0; n < NOUT; ++n) acc[n] = f32x2{0.f, 0.f};

@@ -13,15 +13,11 @@
 //   * tiles: 256 x 320 on eight waves / 128 x 320 (SD channel counts 320 / 640 / 960 / 1280 / 1920 / 2560 are all multiples of 320: no
 //     column waste) and 128 x 128 (everything else: LoRA ranks, 4-channel conv_out, the 16x16 level's Linears, ragged shapes);
 //   * hgemm_tn_kernel contracts over the TOKEN axis with both operands read in place (the LoRA parameter gradients).
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace gadh {
 
 typedef unsigned short u16;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-static __device__ __attribute__((aligned(64))) unsigned int g_zero[16];   // the DMA source of padding / out-of-range chunks
 
 __device__ __forceinline__ float bf2f(u16 h) { return __uint_as_float((unsigned)h << 16); }
 __device__ __forceinline__ u16 f2bf(float f) {          // round to nearest even (NaN kept quiet)
@@ -39,11 +35,6 @@ __device__ __forceinline__ void unpack8(const u32x4& v, float (&f)[8]) {
 }
 __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
   return u32x4{pack2(f[0], f[1]), pack2(f[2], f[3]), pack2(f[4], f[5]), pack2(f[6], f[7])};
-}
-
-__device__ __forceinline__ int xcd_remap(int bid, int nwg) {
-  int xcd = bid & 7, q = nwg >> 3, rr = nwg & 7;
-  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + (bid >> 3);
 }
 
 struct HDev {
@@ -128,12 +119,6 @@ __device__ __forceinline__ void epi_row8(const HDev& p, float* slab, int m, int 
   } else {
     for (int k = 0; k < 8 && n + k < p.N; ++k) epi_store(p, m, n + k, img, v[k]);
   }
-}
-
-template <int N>
-__device__ __forceinline__ void barrier_vm() {          // all but this wave's N youngest vector-memory operations are done, then the
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");   // workgroup barrier - NOT __syncthreads(), whose fence drains every LDS-DMA in flight
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -234,8 +219,7 @@ __global__ __launch_bounds__(WM* WN * 64, (NST == 2 || WM * WN == 8) ? 2 : 1) vo
           ok = ok && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
           const int off = (aoff[i] + yy * p.W + xx) * ld + kk + cha;
           const u16* src = ok ? base + off : zero;
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                           (__attribute__((address_space(3))) void*)(dst + i * (NWA * 1024)), 16, 0, 0);
+          glds16(src, dst + i * (NWA * 1024));
         }
       } else {
         const u16* base = s2 ? p.A2 : p.A;
@@ -243,8 +227,7 @@ __global__ __launch_bounds__(WM* WN * 64, (NST == 2 || WM * WN == 8) ? 2 : 1) vo
         for (int i = 0; i < AI; ++i) {
           const bool ok = live && aok[i] && tail_ok;
           const u16* src = ok ? base + ((s2 ? aoff2[i] : aoff[i]) + kk) : zero;
-          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                           (__attribute__((address_space(3))) void*)(dst + i * (NWA * 1024)), 16, 0, 0);
+          glds16(src, dst + i * (NWA * 1024));
         }
       }
     }
@@ -259,8 +242,7 @@ __global__ __launch_bounds__(WM* WN * 64, (NST == 2 || WM * WN == 8) ? 2 : 1) vo
         const bool ok = live && bok[i] && tail_ok;
         const int o = GATHER == 0 ? (second ? boff2[i] : boff[i]) : boff[i];
         const u16* src = ok ? base + (o + kb) : zero;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                         (__attribute__((address_space(3))) void*)(dst + i * (NWB * 1024)), 16, 0, 0);
+        glds16(src, dst + i * (NWB * 1024));
       }
     }
     if (++sg == p.groups) {
@@ -331,15 +313,13 @@ __global__ __launch_bounds__(WM* WN * 64, (NST == 2 || WM * WN == 8) ? 2 : 1) vo
   if constexpr (NST == 2) {
     if (t0 < t1) {
       stage(0, live0);
-      __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0): the DMA is a VMEM operation
-      __syncthreads();
+      barrier_after_dma();
     }
     for (int st = t0; st < t1; ++st) {
       const int buf = (st - t0) & 1;
       if (st + 1 < t1) stage(buf ^ 1, live0);
       compute(buf);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-      __syncthreads();
+      barrier_after_dma();
     }
   } else {
     constexpr int D = NST - 1;
@@ -415,8 +395,6 @@ __global__ __launch_bounds__(WM* WN * 64, (NST == 2 || WM * WN == 8) ? 2 : 1) vo
 // output window C + s c_seg_stride; L = p.len1 is any length, a stage's rows past the segment's end read the zero block exactly as
 // rows past K do.  Nothing else differs, so a segment's accumulation order is that of a plain launch with K = L and the same split.
 // ---------------------------------------------------------------------------------------------------------------
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ bf16x8 tn_frag(const unsigned char* img, int c0) {      // columns c0 .. c0 + 15 of a [32][128] image, 32 k
   const int lane = threadIdx.x & 63, g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
   const int row = 4 * g + q;                                                          // (row + 16 has the same low three bits)
@@ -461,10 +439,8 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
       const bool kin = kr < p.len1 && !p.dbg_zero;
       const u16* sa = (kin && oka) ? pA + ((long)(k0 + 16 * i) * p.lda + offa) : zero;
       const u16* sb = (kin && okb) ? pB + ((long)(k0 + 16 * i) * p.ldb + offb) : zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sa,
-                                       (__attribute__((address_space(3))) void*)(dst + i * 4096), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)sb,
-                                       (__attribute__((address_space(3))) void*)(dst + OPER + i * 4096), 16, 0, 0);
+      glds16(sa, dst + i * 4096);
+      glds16(sb, dst + OPER + i * 4096);
     }
   };
   f32x4 acc[4][4];
@@ -474,8 +450,7 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (t0 < t1) {
     stage(t0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __syncthreads();
+    barrier_after_dma();
   }
   for (int st = t0; st < t1; ++st) {
     const int buf = (st - t0) & 1;
@@ -494,8 +469,7 @@ __global__ __launch_bounds__(256, 2) void hgemm_tn_kernel(const HDev p) {       
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);
-    __syncthreads();
+    barrier_after_dma();
   }
   // C / D of the 16 x 16 MFMA: column = lane & 15, rows 4 (lane >> 4) + register
   float* slab = p.splitk > 1 ? p.ws + ((long)seg * p.splitk + z) * p.M * p.N : nullptr;
@@ -749,7 +723,6 @@ __global__ void upsample2x_bwd_kernel(const u16* __restrict__ dy, u16* __restric
   }
 }
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_df(float x) {
   return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
 }
@@ -1223,7 +1196,7 @@ static const u16* zero_block() {
   const u16* p = __atomic_load_n(&addr[dev], __ATOMIC_ACQUIRE);
   if (!p) {
     void* sym = nullptr;
-    if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_zero)) != hipSuccess || !sym) return nullptr;
+    if (hipGetSymbolAddress(&sym, HIP_SYMBOL(g_zero_block)) != hipSuccess || !sym) return nullptr;
     p = reinterpret_cast<const u16*>(sym);
     __atomic_store_n(&addr[dev], p, __ATOMIC_RELEASE);
   }

@@ -9,7 +9,7 @@
 // their own chains, (c0 + c1) + (c2 + c3); the wave by xor butterflies; the four waves through LDS in wave order; one
 // pair per workgroup in the workspace; a single-workgroup pass that sums the pairs in index order.  No atomics: the
 // result is a function of (o, k, g, n) alone.
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
 
@@ -21,12 +21,6 @@ inline int wf_blocks(int64_t n) {
   int64_t nv = n / 4;
   int64_t b = gad_ceil_div(nv > 0 ? nv : 1, NT);
   return (int)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
-}
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 __global__ __launch_bounds__(NT) void wf_dots_part_kernel(const float* __restrict__ o, const float* __restrict__ k,

@@ -28,7 +28,7 @@
 // route the planner takes - and the backward runs the mask-free instances; neither touches Philox.
 #include <algorithm>
 
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
 
@@ -37,20 +37,6 @@ constexpr int LD_MB = 2;                // forward: 16-row blocks per wave trip
 constexpr int LD_UNITS = 4;             // column tiles per pass
 constexpr int64_t LD_MAX_SLABS = 256;   // backward: one workgroup per slab, partials = slabs x tiles x 16 x C floats
 constexpr int LD_FWD_BLOCKS = 2048;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
-}
 
 struct Dev {
   const float* x;
@@ -139,7 +125,7 @@ __global__ __launch_bounds__(LD_WAVES * 64) void lora_down_fwd_kernel(const Dev 
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int mb = 0; mb < LD_MB; ++mb) acc[mb][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(am[mb][s], b[s], acc[mb][u], 0, 0, 0);
+          for (int mb = 0; mb < LD_MB; ++mb) acc[mb][u] = mfma16(am[mb][s], b[s], acc[mb][u]);
       }
     }
 
@@ -219,7 +205,7 @@ __global__ __launch_bounds__(LD_WAVES * 64) void lora_down_bwd_kernel(const Dev 
           const float a = (ok[t] && rra < d.r) ? dm[mr[t] * d.r + rra] : 0.f;
           const f32x4 xm = DROP ? xv[t] * k4[t] : xv[t];
 #pragma unroll
-          for (int e = 0; e < 4; ++e) accA[u][e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xm[e], accA[u][e], 0, 0, 0);
+          for (int e = 0; e < 4; ++e) accA[u][e] = mfma16(a, xm[e], accA[u][e]);
         }
         // T = dmid_j[16 rows][16 ranks of rt] A_j[those ranks][64 channels]: tile e, register reg = row m0 + 4 kq + reg, channel c + e
         f32x4 T[4] = {zero, zero, zero, zero};
@@ -228,7 +214,7 @@ __global__ __launch_bounds__(LD_WAVES * 64) void lora_down_bwd_kernel(const Dev 
           const int rr = 16 * rt + 4 * st + kq;
           const float a2 = (rok && rr < d.r) ? dm[mrow * d.r + rr] : 0.f;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) T[e] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, bA[u][st][e], T[e], 0, 0, 0);
+          for (int e = 0; e < 4; ++e) T[e] = mfma16(a2, bA[u][st][e], T[e]);
         }
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg)

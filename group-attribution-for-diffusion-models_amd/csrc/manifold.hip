@@ -11,9 +11,9 @@
 //
 // One engine, manifold_kernel<COVER>: a workgroup of four waves (2 x 2) owns 128 probe rows and walks its share of the 128-column
 // target tiles; per tile the dot products are a 128 x 128 x D contraction on v_mfma_f32_32x32x16_f16 with both operands streamed
-// HBM/L2 -> LDS by LDS-DMA (global_load_lds_dwordx4, two 64-deep stage buffers, vmcnt(0) + barrier per step, the 16-B chunk index
-// XOR-swizzled by the row on the DMA's SOURCE address and on the fragment read - half.hip's staging).  Rows / columns past the
-// end and k >= D are DMA'd from a block of zeros, never from the matrices; a column past the end gets |b|^2 = +inf, so its d2 is
+// HBM/L2 -> LDS by LDS-DMA (glds16, two 64-deep stage buffers, barrier_after_dma per step - gad_dev.h; the 16-B chunk index
+// XOR-swizzled by the row on the DMA's SOURCE address and on the fragment read, as hgemm_kernel of half.hip does).  Rows / columns past the
+// end and k >= D are DMA'd from the zero block, never from the matrices; a column past the end gets |b|^2 = +inf, so its d2 is
 // +inf and takes part in nothing.
 //   radii: each wave passes its 64 x 64 quadrant of d2 through a private LDS patch (aliasing the stage buffers), after which
 //          lane r owns probe row r and keeps the 8 smallest d2 it has seen in registers.
@@ -23,7 +23,7 @@
 #include <hip/hip_fp16.h>
 #include <math.h>
 
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
 
@@ -41,8 +41,6 @@ constexpr int KP = 8;                                    // smallest d2 kept per
 constexpr int TARGET_WG = 512;                           // 256 CUs x 2 resident workgroups
 constexpr int MT = 256;                                  // threads of the pre-pass and merge kernels
 static_assert(BM == BN && DI * RPI * NW == BM, "one dealing of tile rows to DMA instructions for both operands");
-
-static __device__ __attribute__((aligned(64))) unsigned int g_zero[16];   // the DMA source of everything outside the matrices
 
 struct MDev {
   const u16* P; const u16* T;      // probe rows / target rows (the same matrix for the radii)
@@ -95,7 +93,7 @@ __global__ __launch_bounds__(NT, 2) void manifold_kernel(const MDev p) {
   // DMA instruction ii of an operand covers tile rows [8 ii, 8 ii + 8); wave w issues ii = 4 i + w, so the swizzle (row >> 1) & 7 of
   // row 8 ii + lrow does not depend on i: one source chunk per lane
   const int ch = (slot ^ (((wave * RPI + lrow) >> 1) & 7)) * 8;
-  const u16* const zero = reinterpret_cast<const u16*>(g_zero);
+  const u16* const zero = g_zero_block.b16;   // the DMA source of everything outside the matrices
 
   const u16* asrc[DI];
   const u16* bsrc[DI];
@@ -110,14 +108,12 @@ __global__ __launch_bounds__(NT, 2) void manifold_kernel(const MDev p) {
 #pragma unroll
     for (int i = 0; i < DI; ++i) {
       const u16* src = inside && asrc[i] ? asrc[i] + kk : zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(dst + i * (NW * 1024)), 16, 0, 0);
+      glds16(src, dst + i * (NW * 1024));
     }
 #pragma unroll
     for (int i = 0; i < DI; ++i) {
       const u16* src = inside && bsrc[i] ? bsrc[i] + kk : zero;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                       (__attribute__((address_space(3))) void*)(dst + A_BYTES + i * (NW * 1024)), 16, 0, 0);
+      glds16(src, dst + A_BYTES + i * (NW * 1024));
     }
   };
 
@@ -183,13 +179,11 @@ __global__ __launch_bounds__(NT, 2) void manifold_kernel(const MDev p) {
         for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
     stage(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): the DMA is a VMEM operation
-    __syncthreads();
+    barrier_after_dma();
     for (int st = 0; st < steps; ++st) {
       if (st + 1 < steps) stage((st + 1) & 1, (st + 1) * BK);
       compute(st & 1);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-      __syncthreads();                                  // the next stage has landed; every wave is past this stage's reads
+      barrier_after_dma();                              // the next stage has landed; every wave is past this stage's reads
     }
 
     if constexpr (COVER) {

@@ -9,7 +9,6 @@
 //                    Chan's formula - no atomics, deterministic - then normalises its chunk.
 // Forward has a one-pass plan (gn_slab_kernel, below) that reads x once when an (image, channel slab) fits
 // in one workgroup's registers; the two-pass plan remains for the other shapes.
-#include "gad_common.h"
 #include "gad_reduce.h"
 #include "gemm_dev.h"
 
@@ -37,8 +36,6 @@ static Geo make_geo(const gad_groupnorm_args* a) {
   g.nch = (a->HW + g.ppc - 1) / g.ppc;
   return g;
 }
-
-__device__ __forceinline__ float silu_f(float z) { return z / (1.f + expf(-z)); }
 
 // ---------------------------------------------------------------- forward ----
 // Two sources (x2 != NULL): channels [0, C1) of the normalised tensor come from x ([B][HW][C1]) and [C1, C) from x2

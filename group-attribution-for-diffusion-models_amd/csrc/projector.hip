@@ -13,7 +13,7 @@
 //   rademacher: column(t, j) = 64 ct + 16t + j        (Philox column block ct / 2, word 2 (ct & 1) + t / 2, bit 16 (t & 1) + j)
 // so the k index of the MFMA is the slab row p + 4kq + s on both operands.  Each wave writes its slab's partial
 // [G][d] product into the workspace; a second kernel adds the slabs in slab order (no atomics).
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
 
@@ -38,20 +38,6 @@ Plan jl_plan(int64_t P, int32_t d) {
   pl.slab_len = gad_ceil_div(gad_ceil_div(P, JL_CHUNK), want) * JL_CHUNK;
   pl.n_slabs = gad_ceil_div(P, pl.slab_len);
   return pl;
-}
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return c;
 }
 
 // u = (x + 1/2) 2^-32 in (0, 1]: fl32(fl32(x) * 2^-32 + 2^-33), one fma (the restatement in tests/ does the same in fp64)
@@ -129,7 +115,7 @@ __global__ __launch_bounds__(JL_WAVES * 64) void jl_project_kernel(const float* 
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
-        for (int m = 0; m < MB; ++m) acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[m][s], b[t], acc[m][t], 0, 0, 0);
+        for (int m = 0; m < MB; ++m) acc[m][t] = mfma16(a[m][s], b[t], acc[m][t]);
     }
   }
 

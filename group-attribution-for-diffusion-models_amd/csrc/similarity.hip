@@ -24,11 +24,9 @@
 // count depends on N and D only, so a column block computes the same bits whichever M it is launched with.
 #include <math.h>
 
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int BM = 128, BN = 64, BK = 64, NW = 4, NT = NW * 64, TN = BN / 32;
 constexpr int LDT = BK + 4;                              // tile row stride in floats (272 B)

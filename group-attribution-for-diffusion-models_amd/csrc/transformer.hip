@@ -3,7 +3,7 @@
 // HBM-bound: LayerNorm 8 B/elem fwd, 16 B/elem bwd; GEGLU 12 B per output elem fwd.
 // One wave per row (C <= 2048 floats held in registers: 8 float4 per lane), wavefront shuffles for the
 // row moments, no LDS; parameter gradients are per-workgroup partial sums reduced by gad_reduce.
-#include "gad_common.h"
+#include "gad_dev.h"
 #include "gad_reduce.h"
 
 namespace {
@@ -116,7 +116,6 @@ __global__ __launch_bounds__(NT) void ln_bwd_kernel(const float* __restrict__ x,
   }
 }
 
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad(float x) {
   float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
   float pdf = 0.39894228040143268f * expf(-0.5f * x * x);

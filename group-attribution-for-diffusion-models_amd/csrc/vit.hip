@@ -15,7 +15,7 @@
 // function on the host in fp64 (tests, references).  The main kernel copies the rows of the table its patch needs into LDS.
 #include <math.h>
 
-#include "gad_common.h"
+#include "gad_dev.h"
 
 namespace {
 
@@ -180,7 +180,6 @@ __global__ __launch_bounds__(NT) void vit_tokens_kernel(const float* __restrict_
 }
 
 // ---- GELU ----
-__device__ __forceinline__ float gelu_erf(float v) { return 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_quick(float v) { return v / (1.0f + expf(-1.702f * v)); }
 
 template <int V, int KIND>
@@ -192,10 +191,10 @@ __global__ __launch_bounds__(NT) void gelu_kernel(float* __restrict__ x, int64_t
     if constexpr (V == 4) {
       f32x4 v = *reinterpret_cast<f32x4*>(p);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = KIND == 0 ? gelu_erf(v[j]) : gelu_quick(v[j]);
+      for (int j = 0; j < 4; ++j) v[j] = KIND == 0 ? gelu_f(v[j]) : gelu_quick(v[j]);
       *reinterpret_cast<f32x4*>(p) = v;
     } else {
-      *p = KIND == 0 ? gelu_erf(*p) : gelu_quick(*p);
+      *p = KIND == 0 ? gelu_f(*p) : gelu_quick(*p);
     }
   }
 }

@@ -30,21 +30,6 @@ namespace {
 
 template <int N> struct IC : std::integral_constant<int, N> {};
 
-// counted wait for LDS-DMA / loads: all but the N youngest vector-memory operations of this wave are done
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx9");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | 0x0F70);
-}
-// ... followed by the workgroup barrier.  Not __syncthreads(): its workgroup-scope fence makes the compiler drain EVERY
-// outstanding vector-memory operation (vmcnt(0)) - also the LDS-DMA of the stage-steps that are meant to stay in flight.
-// The "memory" clobber keeps the compiler from moving LDS reads across; the stage published here is covered by the count.
-template <int N>
-__device__ __forceinline__ void barrier_vm() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx9");
-  asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
-}
-
 // p.A = V [36][T][Cin] (p.sA0 = T Cin, p.lda = Cin), p.B = U [36][Cout][Cin] (p.sB0 = Cout Cin, p.ldb = Cin), p.C = y (NHWC, p.ldc),
 // p.M = T tiles, p.N = Cout, p.K = Cin (a multiple of 32 SUB); p.fdHoWo / p.fdWo divide by the tiles per image / per tile row
 template <int SUB, int NST>
@@ -261,8 +246,6 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
 // and feeds element j to MFMA step j - the same k assignment for both operands; with the KC tile's XOR swizzle the
 // ds_read_b128 is conflict-free (checked by enumeration).
 // ------------------------------------------------------------------------------------
-__device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 constexpr int EPI2_LD = 36;                      // scratch row stride (floats): rows e and e + 4 of a ds_write_b32 half land 16 banks apart
 constexpr int EPI2_WAVE = 16 * EPI2_LD;
 
