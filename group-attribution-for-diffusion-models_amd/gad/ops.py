@@ -184,20 +184,17 @@ class kernel_flags:
 
     def __init__(self, no_patch=False, tap_major_k=False, gn_two_pass=False, scalar_epilogue=False, general_loaders=False,
                  native_dgrad=False, two_kernel_attn_bwd=False, narrow_attn_fwd=False, no_wino=False, no_wino4=False, no_gn_wino=False):
-        self.native_dgrad, self.two_kernel_attn_bwd, self.narrow_attn_fwd, self.no_wino4 = native_dgrad, two_kernel_attn_bwd, narrow_attn_fwd, no_wino4
-        self.no_gn_wino = no_gn_wino
-        self.gemm = ((_capi.GEMM_NO_PATCH if no_patch else 0) | (_capi.GEMM_TAP_MAJOR_K if tap_major_k else 0)
-                     | (_capi.GEMM_NO_WINO if no_wino else 0)
-                     | (_capi.GEMM_SCALAR_EPILOGUE if scalar_epilogue else 0)
-                     | (_capi.GEMM_GENERAL_LOADERS if general_loaders else 0))
-        self.gn = _capi.GN_TWO_PASS if gn_two_pass else 0
+        gemm = ((_capi.GEMM_NO_PATCH if no_patch else 0) | (_capi.GEMM_TAP_MAJOR_K if tap_major_k else 0)
+                | (_capi.GEMM_NO_WINO if no_wino else 0)
+                | (_capi.GEMM_SCALAR_EPILOGUE if scalar_epilogue else 0)
+                | (_capi.GEMM_GENERAL_LOADERS if general_loaders else 0))
+        self.values = {"gemm": gemm, "gn": _capi.GN_TWO_PASS if gn_two_pass else 0, "native_dgrad": native_dgrad,
+                       "two_kernel_attn_bwd": two_kernel_attn_bwd, "narrow_attn_fwd": narrow_attn_fwd, "no_wino4": no_wino4,
+                       "no_gn_wino": no_gn_wino}
 
     def __enter__(self):
         self.prev = dict(KERNEL_FLAGS)
-        KERNEL_FLAGS["gemm"], KERNEL_FLAGS["gn"], KERNEL_FLAGS["native_dgrad"] = self.gemm, self.gn, self.native_dgrad
-        KERNEL_FLAGS["two_kernel_attn_bwd"], KERNEL_FLAGS["narrow_attn_fwd"] = self.two_kernel_attn_bwd, self.narrow_attn_fwd
-        KERNEL_FLAGS["no_wino4"] = self.no_wino4
-        KERNEL_FLAGS["no_gn_wino"] = self.no_gn_wino
+        KERNEL_FLAGS.update(self.values)
         return self
 
     def __exit__(self, *exc):
@@ -232,17 +229,10 @@ def _out(shape, device):
 def gemm_raw(A, B, Cout, a_mode, b_mode, M, N, K, lda, ldb, ldc, *, geom: Optional[ConvGeom] = None, alpha=1.0,
              bias=None, rowadd=None, rows_per_group=1, residual=None, ldr=0, batch=1, batch_inner=1,
              sA=(0, 0), sB=(0, 0), sC=(0, 0), tile_hint=0, splitk_hint=0, A2=None, a_split=0, B_bf16=None,
-             A_k2=None, B_k2=None, k_split=0, B_wino=None, B_wino4=None, wino_wgrad=False, wino_input=None, force_f32=False,
-             keep_v=None, wino_v=None):
-    """`keep_v` (a list): a forward convolution that takes an F(4x4) Winograd route appends its scratch - the transformed
-    input V at its start - for the weight gradient of the same convolution, which takes it as `wino_v` and skips its own
-    input transform (training: Conv2dFn).
-    `force_f32`: exact fp32 products whatever the process-wide operand precision (small parameter-gradient products).
-    `wino_input(V)`: the caller supplies the F(4x4) Winograd input transform itself (GroupNorm writing V directly,
-    `gn_silu_conv3x3_raw`): if the planner puts this launch on an F(4x4) route the callback is run on the route's scratch and
-    the convolution starts behind its input stage; on any other route nothing is launched.
-    -> False in exactly that case (`wino_input` given and the planner chose another route); True after every launch."""
-    lib = _capi.load()
+             A_k2=None, B_k2=None, k_split=0, force_f32=False, launch=True) -> GemmArgs:
+    """One fp32 contraction: fills its argument struct (the stream's workspace attached) and launches it (`_launch_gemm`).
+    `launch=False`: only the arguments - the convolution wrappers put a Winograd offer between the two.
+    `force_f32`: exact fp32 products whatever the process-wide operand precision (small parameter-gradient products)."""
     ws = workspace(A.device)
     a = GemmArgs()
     a.A, a.B, a.C = A.data_ptr(), B.data_ptr(), Cout.data_ptr()
@@ -271,44 +261,22 @@ def gemm_raw(A, B, Cout, a_mode, b_mode, M, N, K, lda, ldb, ldc, *, geom: Option
     if A_k2 is not None:            # K-concatenated operands (fused LoRA): k >= k_split reads A_k2 / B_k2
         a.A_k2, a.B_k2, a.k_split = A_k2.data_ptr(), B_k2.data_ptr(), k_split
         a.lda_k2, a.ldb_k2 = A_k2.shape[-1], B_k2.shape[-1]
-    if B_wino is not None or B_wino4 is not None:      # Winograd routes: the planner says whether this launch takes one and how much scratch it needs
-        a.B_wino, a.B_wino4 = _ptr(B_wino), _ptr(B_wino4)
-        need = lib.gad_gemm_wino_bytes(C.byref(a))
-        if need:
-            V = _scratch("wino", need, A.device)      # stream-ordered: safe to drop after the launch
-            a.wino_ws, a.wino_ws_bytes = V.data_ptr(), need
-            if keep_v is not None and a.B_wino4 and lib.gad_gemm_kernel_id(C.byref(a)) == 6:
-                keep_v.append(V)
-        else:
-            a.B_wino = a.B_wino4 = None
-    if wino_wgrad:                   # 3x3 weight gradient: the F(4x4) Winograd form where the planner models it faster
-        a.flags |= _capi.GEMM_WINO_WGRAD
-        need = lib.gad_gemm_wino_bytes(C.byref(a))
-        if need:
-            V = _scratch("wino", need, A.device)
-            a.wino_ws, a.wino_ws_bytes = V.data_ptr(), need
-            if wino_v is not None and wino_v.numel() >= 36 * (K // 16) * geom.C * 4:      # the forward launch's V: [36][pixels / 16][Cin] fp32
-                a.B_wino4 = wino_v.data_ptr()
-                a.flags |= _capi.GEMM_WINO_SKIP_INPUT
-        else:
-            a.flags &= ~_capi.GEMM_WINO_WGRAD
-    if wino_input is not None:
-        if lib.gad_gemm_kernel_id(C.byref(a)) != 6 or not a.wino_ws:
-            return False
-        wino_input(V)
-        a.flags |= _capi.GEMM_WINO_SKIP_INPUT
-    if ROUTE_STATS is not None and (a.B_wino4 or a.flags & _capi.GEMM_WINO_WGRAD):      # tools/wino_route_stats.py
-        key = (lib.gad_gemm_kernel_id(C.byref(a)), M, N, K, bool(a.flags & _capi.GEMM_WINO_SKIP_INPUT), torch.is_grad_enabled())
-        ROUTE_STATS[key] = ROUTE_STATS.get(key, 0) + 1
+    if launch:
+        _launch_gemm(a, A.device, batch)
+    return a
+
+
+def _launch_gemm(a, device, batch=1):
+    """What every fp32 contraction launch shares: the canary workspace, the profiler, gad_gemm."""
+    lib = _capi.load()
     if SCRATCH_ALLOC is not None:    # canary runs: the workspace at exactly the size the planner asks for this launch
         need = lib.gad_gemm_workspace_bytes(C.byref(a))
-        ws = _scratch("ws", need, A.device) if need else None
+        ws = _scratch("ws", need, device) if need else None
         a.ws, a.ws_bytes = (ws.data_ptr() if need else None), need
     if PROFILER is not None:
         PROFILER.gemm(lib, a, batch)
-        return True
+        return
     check(lib.gad_gemm(C.byref(a), _stream()), "gad_gemm")
-    return True
 
 
 class GemmProfiler:
@@ -435,17 +403,15 @@ def _conv_out_size(h, k, stride, pad_lo, pad_hi):
     return (h + pad_lo + pad_hi - k) // stride + 1
 
 
-def conv2d_fwd_raw(x, w, bias, stride=1, pad=(1, 1, 1, 1), upsample=False, rowadd=None, residual=None,
-                   tile_hint=0, splitk_hint=0, x2=None, wino_input=None, keep_v=None):
-    """x [B,H,W,Cin] -> y [B,Ho,Wo,Cout]; pad = (top, bottom, left, right).
-    x2 [B,H,W,C2]: the conv input is cat([x, x2], channels) without materialising it (UpBlock2D's skip concat)."""
-    _req(x, "conv x")
-    Bn, H, W, C1 = x.shape
+def _conv_fwd_args(x, x_shape, w, bias, stride, pad, upsample, rowadd, residual, tile_hint, splitk_hint, x2=None):
+    """-> (y, its gad_gemm arguments) for the forward convolution of the [B,H,W,C1] tensor at `x` - only its address and device
+    are read, so the caller may hold it in another form."""
+    Bn, H, W, C1 = x_shape
     Cin = C1
     if x2 is not None:
         _req(x2, "conv x2")
-        if x2.shape[:3] != x.shape[:3]:
-            raise _capi.GadError(f"conv x2 {tuple(x2.shape)} does not match x {tuple(x.shape)}")
+        if x2.shape[:3] != x_shape[:3]:
+            raise _capi.GadError(f"conv x2 {tuple(x2.shape)} does not match x {tuple(x_shape)}")
         Cin = C1 + x2.shape[-1]
     wk = weight_krsc(w)
     Cout, KH, KW, wc = wk.shape
@@ -458,70 +424,27 @@ def conv2d_fwd_raw(x, w, bias, stride=1, pad=(1, 1, 1, 1), upsample=False, rowad
     g = ConvGeom(H, W, Cin, C1, Ho, Wo, KH, KW, stride, pad[0], pad[2], int(upsample))
     if residual is not None:
         _req(residual, "conv residual")
-    # Winograd forms of the weight: F(4x4) wherever the output map is a multiple of 4 (it measured faster than F(2x2) at every
-    # shape of tools/ab_winograd.py), F(2x2) for the other even maps; the library's planner still decides per launch
-    wino_ok = (KH == 3 and KW == 3 and stride == 1 and x2 is None and tile_hint in (0, 7, 8, 9, 10, 11) and splitk_hint == 0
-               and tuple(pad) == (1, 1, 1, 1))
-    f4_maps = Ho % 4 == 0 and Wo % 4 == 0 and not KERNEL_FLAGS.get("no_wino4")
-    launched = gemm_raw(x, wk, y, A_CONV, B_KC, Bn * Ho * Wo, Cout, KH * KW * Cin, 0, KH * KW * Cin, Cout, geom=g,
-             bias=bias, rowadd=rowadd, rows_per_group=Ho * Wo, residual=residual, ldr=Cout,
-             tile_hint=tile_hint, splitk_hint=splitk_hint, A2=x2, a_split=C1, wino_input=wino_input, keep_v=keep_v,
-             B_wino=wino_weight(w, 2) if (wino_ok and (tile_hint == 7 or (tile_hint == 0 and not f4_maps))) else None,
-             B_wino4=wino_weight(w, 4) if (wino_ok and tile_hint != 7 and f4_maps) else None,
-             B_bf16=bf16_weight(w) if (OPERAND_PRECISION[0] >= 1 and KH == 3 and Cin % 32 == 0 and x2 is None
-                                       and not torch.cuda.is_current_stream_capturing()) else None)
-    return y if launched is not False else None
+    return y, gemm_raw(x, wk, y, A_CONV, B_KC, Bn * Ho * Wo, Cout, KH * KW * Cin, 0, KH * KW * Cin, Cout, geom=g,
+                       bias=bias, rowadd=rowadd, rows_per_group=Ho * Wo, residual=residual, ldr=Cout,
+                       tile_hint=tile_hint, splitk_hint=splitk_hint, A2=x2, a_split=C1, launch=False,
+                       B_bf16=bf16_weight(w) if (OPERAND_PRECISION[0] >= 1 and KH == 3 and Cin % 32 == 0 and x2 is None
+                                                 and not torch.cuda.is_current_stream_capturing()) else None)
 
 
-def gn_silu_conv3x3_raw(x, x2, gamma, beta, G, eps, w, bias, rowadd=None, residual=None, tile_hint=0):
-    """conv3x3(SiLU(GroupNorm(cat([x, x2])))) + bias + rowadd + residual, forward only (the sampler's ResnetBlock2D halves:
-    reference diffusers ResnetBlock2D.forward, norm1 -> silu -> conv1 (+ temb) and norm2 -> silu -> conv2 (+ shortcut)).
-    Where the convolution takes an F(4x4) Winograd route and the norm has a plan for it (`gad_groupnorm_wino4_ok`), GroupNorm
-    writes the route's transformed input V directly - the normalised activation never exists in HBM and the route's input
-    transform launch disappears; otherwise the two ordinary launches run.  Same results to fp32 rounding either way."""
-    _req(x, "groupnorm x")
-    Bn, H, W, C1 = x.shape
-    Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
-    lib = _capi.load()
-
-    def plain():
-        h = group_norm_cat_raw(x, x2, gamma, beta, G, eps, True) if x2 is not None else group_norm(x, gamma, beta, G, eps, True)
-        return conv2d_fwd_raw(h, w, bias, 1, (1, 1, 1, 1), False, rowadd=rowadd, residual=residual, tile_hint=tile_hint)
-    if (torch.is_grad_enabled() or tuple(w.shape[2:]) != (3, 3) or w.shape[1] != Cin or OPERAND_PRECISION[0] != 0 or KERNEL_FLAGS["gn"]
-            or KERNEL_FLAGS.get("no_gn_wino") or H % 4 or W % 4):
-        return plain()
-    mean = torch.empty((Bn, G), device=x.device, dtype=torch.float32)
-    rstd = torch.empty_like(mean)
-    a = GroupNormArgs()
-    a.x, a.gamma, a.beta, a.mean, a.rstd = x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr()
-    a.B, a.HW, a.C, a.G, a.eps, a.silu = Bn, H * W, Cin, G, eps, 1
-    if x2 is not None:
-        _req(x2, "groupnorm x2")
-        a.x2, a.C1 = x2.data_ptr(), C1
-    if not lib.gad_groupnorm_wino4_ok(C.byref(a), W):
-        return plain()
-
-    def fill(V):
-        check(lib.gad_groupnorm_silu_wino4(C.byref(a), V.data_ptr(), W, _stream()), "gad_groupnorm_silu_wino4")
-    # the convolution's "input" is only a shape here: its first stage is replaced by `fill`
-    y = conv2d_fwd_raw(_ShapeOnly(x, (Bn, H, W, Cin)), w, bias, 1, (1, 1, 1, 1), False, rowadd=rowadd, residual=residual,
-                       tile_hint=tile_hint, wino_input=fill)
-    return y if y is not None else plain()
-
-
-class _ShapeOnly:
-    """Stands in for the input tensor of a convolution whose input stage another kernel has taken over: shape, device and a
-    valid aligned pointer (never dereferenced)."""
-
-    def __init__(self, t, shape):
-        self._t, self.shape, self.device, self.dtype = t, tuple(shape), t.device, t.dtype
-        self.is_cuda = t.is_cuda
-
-    def data_ptr(self):
-        return self._t.data_ptr()
-
-    def is_contiguous(self):
-        return True
+def conv2d_fwd_raw(x, w, bias, stride=1, pad=(1, 1, 1, 1), upsample=False, rowadd=None, residual=None,
+                   tile_hint=0, splitk_hint=0, x2=None, keep_v=None):
+    """x [B,H,W,Cin] -> y [B,Ho,Wo,Cout]; pad = (top, bottom, left, right).
+    x2 [B,H,W,C2]: the conv input is cat([x, x2], channels) without materialising it (UpBlock2D's skip concat).
+    `keep_v` (a list): a launch that takes an F(4x4) Winograd route appends its scratch - the transformed input V at its start -
+    for the weight gradient of the same convolution, which takes it as `wino_v` and skips its own input transform (Conv2dFn)."""
+    _req(x, "conv x")
+    y, a = _conv_fwd_args(x, x.shape, w, bias, stride, pad, upsample, rowadd, residual, tile_hint, splitk_hint, x2)
+    form = wino_prefilter(w.shape[2:], stride, pad, x2 is not None, w.shape[0], w.shape[1], y.shape[1:3], tile_hint, splitk_hint)[0]
+    V = _offer_wino(a, x.device, w, form)
+    if keep_v is not None and V is not None and form == 4:
+        keep_v.append(V)
+    _launch_gemm(a, x.device)
+    return y
 
 
 def bf16_weight(w):
@@ -553,7 +476,7 @@ def dgrad_as_forward(w, stride, pad) -> bool:
     buffer (training.flatten_params: ONE launch per optimizer step rotates every 3x3 weight of the model,
     `gad_rotate_conv3x3`).  `kernel_flags(native_dgrad=True)` keeps the data-gradient kernels (A/B tools, tests)."""
     return (tuple(w.shape[2:]) == (3, 3) and stride == 1 and tuple(pad) == (1, 1, 1, 1) and w.shape[0] % 32 == 0
-            and w.shape[1] >= 64 and (not w.requires_grad or _in_flat_buffer(w)) and not KERNEL_FLAGS.get("native_dgrad"))
+            and w.shape[1] >= 64 and (not w.requires_grad or _in_flat_buffer(w)) and not KERNEL_FLAGS["native_dgrad"])
 
 
 def _rotate_conv3x3(flat, out, table, tiles):
@@ -604,8 +527,112 @@ def _conv3x3_residents(flat):
     return r
 
 
+# ----------------------------------------------------------------------------------
+# Winograd routes of the 3x3 convolutions: the host offers (`wino_prefilter`), the library's planner decides per launch, and
+# the offer RETURNS the scratch the planner asked for - its caller holds it until the launch is enqueued (stream-ordered:
+# safe to drop then) or hands it on as `keep_v`.
+# ----------------------------------------------------------------------------------
 def _wino_ok(co, ci):
     return ci % 32 == 0 and co % 4 == 0 and co >= 64
+
+
+def wino_prefilter(kernel, stride, pad, two_source, Cout, Cin, out_map, tile_hint=0, splitk_hint=0):
+    """-> (form, wgrad): the Winograd form of the weight the host offers a FORWARD launch of this convolution - 0 none, 2 F(2x2),
+    4 F(4x4) - and whether it opts the convolution's WEIGHT GRADIENT into its F(4x4) form.  A pre-filter: it keeps the host
+    from transforming weights and asking where the answer cannot be yes; the planner decides (`gad_gemm_wino_bytes`), and never
+    takes what this withholds (tests/test_conv_launch_cpu.py).  F(4x4) wherever the output map is a multiple of 4 (it measured
+    faster than F(2x2) at every shape of tools/ab_winograd.py), F(2x2) for the other maps; tile hints 7 / 8-11 force a form."""
+    flags = KERNEL_FLAGS["gemm"]
+    if (tuple(kernel) != (3, 3) or stride != 1 or tuple(pad) != (1, 1, 1, 1) or splitk_hint != 0 or OPERAND_PRECISION[0] >= 1
+            or flags & (_capi.GEMM_NO_WINO | _capi.GEMM_NO_PATCH | _capi.GEMM_SCALAR_EPILOGUE | _capi.GEMM_TAP_MAJOR_K)):
+        return 0, False
+    f4_maps = out_map[0] % 4 == 0 and out_map[1] % 4 == 0 and not KERNEL_FLAGS["no_wino4"]
+    wgrad = f4_maps and tile_hint in (0, 8) and not flags & _capi.GEMM_GENERAL_LOADERS
+    if two_source or not _wino_ok(Cout, Cin) or tile_hint not in (0, 7, 8, 9, 10, 11):
+        return 0, wgrad
+    if f4_maps and tile_hint != 7:
+        return 4, wgrad
+    return (2 if tile_hint in (0, 7) else 0), wgrad
+
+
+def _count_wino4(a, kid):
+    if ROUTE_STATS is not None:      # tools/wino_route_stats.py
+        key = (kid, a.M, a.N, a.K, bool(a.flags & _capi.GEMM_WINO_SKIP_INPUT), torch.is_grad_enabled())
+        ROUTE_STATS[key] = ROUTE_STATS.get(key, 0) + 1
+
+
+def _offer_wino(a, device, w, form, supplied=False):
+    """The forward offer: attach the weight's Winograd `form`, ask the planner once, allocate the scratch it wants -> that scratch
+    (the launch is on the form's route), or None with the pointers cleared.  `supplied`: the caller's own kernel writes the
+    F(4x4) input image V into the scratch and the launch starts behind its input stage; any other route counts as declined."""
+    U = wino_weight(w, form, offered=True) if form else None
+    if U is None:
+        return None
+    setattr(a, "B_wino" if form == 2 else "B_wino4", U.data_ptr())
+    need = _capi.load().gad_gemm_wino_bytes(C.byref(a))
+    if not need or (supplied and form != 4):
+        a.B_wino = a.B_wino4 = None
+        return None
+    V = _scratch("wino", need, device)
+    a.wino_ws, a.wino_ws_bytes = V.data_ptr(), need
+    if form == 4:
+        a.flags |= _capi.GEMM_WINO_SKIP_INPUT if supplied else 0
+        _count_wino4(a, 6)
+    return V
+
+
+def _opt_in_wino_wgrad(a, device, wino_v):
+    """The weight gradient's opt-in, in the same shape: -> the scratch, or None with the flag cleared.  `wino_v`, the scratch a
+    forward launch kept, replaces the input transform if it holds the whole image V: [36][pixels / 16][Cin] fp32."""
+    a.flags |= _capi.GEMM_WINO_WGRAD
+    need = _capi.load().gad_gemm_wino_bytes(C.byref(a))
+    if not need:
+        a.flags &= ~_capi.GEMM_WINO_WGRAD
+        return None
+    ws = _scratch("wino", need, device)
+    a.wino_ws, a.wino_ws_bytes = ws.data_ptr(), need
+    if wino_v is not None and wino_v.numel() >= 36 * (a.K // 16) * a.g.C * 4:
+        a.B_wino4 = wino_v.data_ptr()
+        a.flags |= _capi.GEMM_WINO_SKIP_INPUT
+    _count_wino4(a, 7)
+    return ws
+
+
+def gn_silu_conv3x3_raw(x, x2, gamma, beta, G, eps, w, bias, rowadd=None, residual=None, tile_hint=0):
+    """conv3x3(SiLU(GroupNorm(cat([x, x2])))) + bias + rowadd + residual, forward only (the sampler's ResnetBlock2D halves:
+    reference diffusers ResnetBlock2D.forward, norm1 -> silu -> conv1 (+ temb) and norm2 -> silu -> conv2 (+ shortcut)).
+    Where the convolution takes an F(4x4) Winograd route and the norm has a plan for it (`gad_groupnorm_wino4_ok`), GroupNorm
+    writes the route's transformed input V directly - the normalised activation never exists in HBM and the route's input
+    transform launch disappears; otherwise the two ordinary launches run.  Same results to fp32 rounding either way."""
+    _req(x, "groupnorm x")
+    Bn, H, W, C1 = x.shape
+    Cin = C1 + (x2.shape[-1] if x2 is not None else 0)
+    lib = _capi.load()
+
+    def plain():
+        h = group_norm_cat_raw(x, x2, gamma, beta, G, eps, True) if x2 is not None else group_norm(x, gamma, beta, G, eps, True)
+        return conv2d_fwd_raw(h, w, bias, 1, (1, 1, 1, 1), False, rowadd=rowadd, residual=residual, tile_hint=tile_hint)
+    form = wino_prefilter(w.shape[2:], 1, (1, 1, 1, 1), False, w.shape[0], Cin, (H, W), tile_hint)[0]
+    if torch.is_grad_enabled() or w.shape[1] != Cin or KERNEL_FLAGS["gn"] or KERNEL_FLAGS["no_gn_wino"] or H % 4 or W % 4 or not form:
+        return plain()
+    mean = torch.empty((Bn, G), device=x.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    gn = GroupNormArgs()
+    gn.x, gn.gamma, gn.beta, gn.mean, gn.rstd = x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(), rstd.data_ptr()
+    gn.B, gn.HW, gn.C, gn.G, gn.eps, gn.silu = Bn, H * W, Cin, G, eps, 1
+    if x2 is not None:
+        _req(x2, "groupnorm x2")
+        gn.x2, gn.C1 = x2.data_ptr(), C1
+    if not lib.gad_groupnorm_wino4_ok(C.byref(gn), W):
+        return plain()
+    # the convolution's input is only a shape here: its first stage is the norm's launch
+    y, a = _conv_fwd_args(x, (Bn, H, W, Cin), w, bias, 1, (1, 1, 1, 1), False, rowadd, residual, tile_hint, 0)
+    V = _offer_wino(a, x.device, w, form, supplied=True)
+    if V is None:
+        return plain()
+    check(lib.gad_groupnorm_silu_wino4(C.byref(gn), V.data_ptr(), W, _stream()), "gad_groupnorm_silu_wino4")
+    _launch_gemm(a, x.device)
+    return y
 
 
 def _wino_shadow(src, items, f):
@@ -623,17 +650,15 @@ def _wino_shadow(src, items, f):
                                            "gad_wino_weights"), where)
 
 
-def wino_weight(w, f=2):
+def wino_weight(w, f=2, offered=False):
     """The Winograd form U = G w G^T of a 3x3 conv weight: [16][Cout][Cin] for F(2x2, 3x3) (`gad_wino_weights`, f = 2) or
-    [36][Cout][Cin] for F(4x4, 3x3) (`gad_wino4_weights`, f = 4); None for a weight the Winograd kernels do not take
-    (Cin % 32, Cout % 4, < 64 output channels, bf16-operand mode, the no_wino switch).  A weight living in a flat parameter
-    buffer - or in the rotated shadow of one, for the data gradients - is served from ONE transformed shadow of that buffer
-    per form, refreshed by a single launch when the weights changed (`Shadow.fresh_for`); any other weight keeps its own
-    transform, rewritten in place per version."""
+    [36][Cout][Cin] for F(4x4, 3x3) (`gad_wino4_weights`, f = 4); None for a weight no forward launch is offered that form of
+    (`wino_prefilter`: Cin % 32, Cout % 4, < 64 output channels, bf16-operand mode, the no_wino switches).  A weight living in
+    a flat parameter buffer - or in the rotated shadow of one, for the data gradients - is served from ONE transformed shadow of
+    that buffer per form, refreshed by a single launch when the weights changed (`Shadow.fresh_for`); any other weight keeps
+    its own transform, rewritten in place per version.  `offered`: the caller has asked the pre-filter for this launch."""
     co, ci = w.shape[0], w.shape[1]
-    if (tuple(w.shape[2:]) != (3, 3) or not _wino_ok(co, ci) or OPERAND_PRECISION[0] >= 1
-            or KERNEL_FLAGS["gemm"] & (_capi.GEMM_NO_WINO | _capi.GEMM_NO_PATCH | _capi.GEMM_SCALAR_EPILOGUE | _capi.GEMM_TAP_MAJOR_K)
-            or (f == 4 and KERNEL_FLAGS.get("no_wino4"))):
+    if not offered and wino_prefilter(w.shape[2:], 1, (1, 1, 1, 1), False, co, ci, (f, f))[0] != f:
         return None
     attr = "_gad_wino" if f == 2 else "_gad_wino4"
     if _in_flat_buffer(w):
@@ -660,6 +685,13 @@ def refresh_wino(module):
                     wino_weight(p, f)
 
 
+def _dense_1x1(KH, KW, stride, pad, upsample, Cin, Cout) -> bool:
+    """A 1x1 / stride-1 convolution (ResNet shortcuts, proj_in / proj_out of the SD transformer blocks) is a dense GEMM over
+    the pixel rows: its gradients run on the lean dense loaders instead of the im2col gathers."""
+    return (KH == 1 and KW == 1 and stride == 1 and tuple(pad) == (0, 0, 0, 0) and not upsample and Cin % 4 == 0 and Cout % 4 == 0
+            and not KERNEL_FLAGS["gemm"] & _capi.GEMM_GENERAL_LOADERS)
+
+
 def two_source_ok(c1: int, c2: int) -> bool:
     """Can conv2d_fwd_raw(x, ..., x2=) gather this channel split? (32-channel K steps must not straddle it)"""
     return c1 % 32 == 0 and c2 % 32 == 0
@@ -674,10 +706,7 @@ def conv2d_dgrad_raw(dy, w, x_shape, stride=1, pad=(1, 1, 1, 1), upsample=False,
     _, Ho, Wo, _ = dy.shape
     He, We = (2 * H, 2 * W) if upsample else (H, W)
     dxe = _out((Bn, He, We, Cin), dy.device)
-    if (KH == 1 and KW == 1 and stride == 1 and tuple(pad) == (0, 0, 0, 0) and not upsample and Cin % 4 == 0 and Cout % 4 == 0
-            and not KERNEL_FLAGS["gemm"] & _capi.GEMM_GENERAL_LOADERS):
-        # a 1x1 / stride-1 convolution (ResNet shortcuts, proj_in / proj_out of the SD transformer blocks) is a dense
-        # GEMM over the pixel rows: dx = dy W on the lean dense loaders instead of the transposed im2col gather
+    if _dense_1x1(KH, KW, stride, pad, upsample, Cin, Cout):      # dx = dy W
         gemm_raw(dy, wk, dxe, A_KC, B_MC, Bn * H * W, Cin, Cout, Cout, Cin, Cin, tile_hint=tile_hint, splitk_hint=splitk_hint)
         return dxe
     g = ConvGeom(Ho, Wo, Cout, Cout, He, We, KH, KW, stride, pad[0], pad[2], 0)
@@ -704,17 +733,15 @@ def conv2d_wgrad_raw(dy, x, w_like, stride=1, pad=(1, 1, 1, 1), upsample=False, 
     Cout, _, KH, KW = w_like.shape
     _, Ho, Wo, _ = dy.shape
     dwk = _out((Cout, KH, KW, Cin), dy.device) if out is None else weight_krsc(out)
-    if (KH == 1 and KW == 1 and stride == 1 and tuple(pad) == (0, 0, 0, 0) and not upsample and Cin % 4 == 0 and Cout % 4 == 0
-            and not KERNEL_FLAGS["gemm"] & _capi.GEMM_GENERAL_LOADERS):
+    if _dense_1x1(KH, KW, stride, pad, upsample, Cin, Cout):
         gemm_raw(dy, x, dwk, A_MC, B_MC, Cout, Cin, Bn * H * W, Cout, Cin, Cin, tile_hint=tile_hint, splitk_hint=splitk_hint)   # dW = dy^T x
         return dwk.permute(0, 3, 1, 2)
     g = ConvGeom(H, W, Cin, Cin, Ho, Wo, KH, KW, stride, pad[0], pad[2], int(upsample))
-    wino = (KH == 3 and KW == 3 and stride == 1 and tuple(pad) == (1, 1, 1, 1) and tile_hint in (0, 8) and splitk_hint == 0
-            and Ho % 4 == 0 and Wo % 4 == 0 and OPERAND_PRECISION[0] == 0 and not KERNEL_FLAGS.get("no_wino4")
-            and not KERNEL_FLAGS["gemm"] & (_capi.GEMM_NO_WINO | _capi.GEMM_NO_PATCH | _capi.GEMM_SCALAR_EPILOGUE | _capi.GEMM_TAP_MAJOR_K
-                                            | _capi.GEMM_GENERAL_LOADERS))
-    gemm_raw(dy, x, dwk, A_MC, B_CONV, Cout, KH * KW * Cin, Bn * Ho * Wo, Cout, 0, KH * KW * Cin, geom=g,
-             tile_hint=tile_hint, splitk_hint=splitk_hint, wino_wgrad=wino, wino_v=wino_v)
+    a = gemm_raw(dy, x, dwk, A_MC, B_CONV, Cout, KH * KW * Cin, Bn * Ho * Wo, Cout, 0, KH * KW * Cin, geom=g,
+                 tile_hint=tile_hint, splitk_hint=splitk_hint, launch=False)
+    if wino_prefilter((KH, KW), stride, pad, False, Cout, Cin, (Ho, Wo), tile_hint, splitk_hint)[1]:
+        scratch = _opt_in_wino_wgrad(a, dy.device, wino_v)      # noqa: F841  (held until the launch is enqueued)
+    _launch_gemm(a, dy.device)
     return dwk.permute(0, 3, 1, 2)
 
 
@@ -1423,7 +1450,7 @@ def attention_fwd_raw(q, k, v, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, need_lse=Tru
     lse = _out((Bn, heads, Tq), q.device) if need_lse else None
     a = _attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, ldq, ldk, ldv, Tq * ldq, Tk * ldk, Tk * ldv, scale)
     a.operand_precision = 1 if OPERAND_PRECISION[0] else 0         # bf16 modes: bf16-operand instance of the fused kernel
-    a.flags = _capi.ATTN_NARROW_FWD if KERNEL_FLAGS.get("narrow_attn_fwd") else 0
+    a.flags = _capi.ATTN_NARROW_FWD if KERNEL_FLAGS["narrow_attn_fwd"] else 0
     if PROFILER is not None:
         PROFILER.attention(_capi.load().gad_attention_fwd, a, "fwd")
     else:
@@ -1462,7 +1489,7 @@ class AttentionCoreFn(torch.autograd.Function):
         a = _attention_args(q, k, v, o, lse, Bn, heads, Tq, Tk, d, Cq, Cq, Cq, Tq * Cq, Tk * Cq, Tk * Cq, ctx.scale)
         _attention_grad_args(a, do, delta, dq, dk, dv, Cq, Tq * Cq, Tk * Cq)
         a.operand_precision = ctx.prec                  # the precision the forward's LSE was computed in
-        a.flags = _capi.ATTN_TWO_KERNEL_BWD if KERNEL_FLAGS.get("two_kernel_attn_bwd") else 0
+        a.flags = _capi.ATTN_TWO_KERNEL_BWD if KERNEL_FLAGS["two_kernel_attn_bwd"] else 0
         need = _capi.load().gad_attention_bwd_workspace_bytes(C.byref(a))
         if need:                                         # dQ partial slabs of the single-pass kernel (one per key block)
             slabs = _scratch("attn_ws", need, q.device)

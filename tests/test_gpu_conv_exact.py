@@ -157,16 +157,18 @@ class Forward:
             expect[wide.lead:wide.lead + wide.n].view(wide.t.shape)[..., row.c0:row.c0 + row.Cout] = want
             ops.conv_krsc_raw(self.x.t, self.w.t, bias, row.KH, row.KW, row.stride, row.pad[0], row.pad[2], out=wide.t, c0=row.c0)
             return wide.buf, expect, wide.t[..., row.c0:row.c0 + row.Cout]
-        from gad._capi import A_CONV, B_KC, ConvGeom                       # ldx: gemm_raw with the geometry spelt out
+        from gad._capi import A_CONV, B_KC, ConvGeom                       # ldx: the convolution's launch with the geometry spelt out
         y = ops._out((row.B, row.Ho, row.Wo, row.Cout), dev)
         Kd = row.KH * row.KW * row.Cin
         three = (row.KH, row.KW, row.stride, row.pad) == (3, 3, 1, CC.P1)
-        ops.gemm_raw(self.x.t, self.w.t, y, A_CONV, B_KC, row.B * row.Ho * row.Wo, row.Cout, Kd, 0, Kd, row.Cout,
-                     geom=ConvGeom(row.H, row.W, row.Cin, row.Cin + row.ldx_pad, row.Ho, row.Wo, row.KH, row.KW, row.stride,
-                                   row.pad[0], row.pad[2], int(row.ups)),
-                     bias=bias, rowadd=rowadd, rows_per_group=row.Ho * row.Wo, residual=residual, ldr=row.Cout, tile_hint=hint,
-                     splitk_hint=splitk, B_wino=ops.wino_weight(self.w_logical, 2) if (three and hint in (0, 7) and splitk == 0) else None,
-                     B_bf16=ops.bf16_weight(self.w_logical) if (prec == "bf16" and three and row.Cin % 32 == 0) else None)
+        a = ops.gemm_raw(self.x.t, self.w.t, y, A_CONV, B_KC, row.B * row.Ho * row.Wo, row.Cout, Kd, 0, Kd, row.Cout,
+                         geom=ConvGeom(row.H, row.W, row.Cin, row.Cin + row.ldx_pad, row.Ho, row.Wo, row.KH, row.KW, row.stride,
+                                       row.pad[0], row.pad[2], int(row.ups)),
+                         bias=bias, rowadd=rowadd, rows_per_group=row.Ho * row.Wo, residual=residual, ldr=row.Cout, tile_hint=hint,
+                         splitk_hint=splitk, launch=False,
+                         B_bf16=ops.bf16_weight(self.w_logical) if (prec == "bf16" and three and row.Cin % 32 == 0) else None)
+        scratch = ops._offer_wino(a, dev, self.w_logical, 2 if (three and hint in (0, 7) and splitk == 0) else 0)      # noqa: F841  (held until the launch is enqueued)
+        ops._launch_gemm(a, dev)
         return y, want, y
 
 
