@@ -1,6 +1,7 @@
-// Device-side building blocks of the fp32 contraction kernels of gemm_f32.hip and wino4_fused.hip (gfx950 only):
-// launch-argument struct, tile slots and loaders, the XOR-swizzled KC tile image and its fragment reads, Winograd transforms.
-// The LDS-DMA issue, the waits and the zero block are gad_dev.h's.
+// Device-side building blocks of the fp32 contraction kernels of gemm_f32.hip, winograd.hip and wino4_fused.hip (gfx950 only):
+// launch-argument struct, tile slots and loaders, the XOR-swizzled KC tile image and its fragment reads, the K step, the
+// epilogue; and the declarations the planner shares with the Winograd launchers.  The Winograd device pieces are wino_dev.h's;
+// the LDS-DMA issue, the waits and the zero block are gad_dev.h's.
 #pragma once
 #include "gad_dev.h"
 
@@ -122,34 +123,188 @@ __device__ __forceinline__ f32x4 read_frag(const float* lds, int row, int g, int
   }
 }
 
-// dense [row][k] rows by LDS-DMA with a 64-bit step offset (position x panel stride + k): rows beyond the operand clamp
-// to the last one (they feed outputs the epilogue never stores)
-template <int ROWS>
-struct WinoKC : KCSlots<ROWS> {
-  using S = KCSlots<ROWS>;
-  const float* ptr[S::NS];
-  long off;
-  __device__ void init(const float* b, int ld, int row0, int nrows) {
+// ------------------------------------------------------------------------------------
+// Epilogue shared by every contraction kernel: the wave block's accumulators (C/D map: col = lane & 31,
+// row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) go to C with alpha, bias[n], rowadd[m / rows_per_group][n] and
+// residual[m][n] fused - or, for a split of a split-K launch (direct = false), raw to the workspace slab.
+//
+// The C/D map gives a lane ONE column and 16 rows, so stores straight from the accumulators are 64 dword wave-stores per
+// 32 x 128 block, and the epilogue's time is the count of those instructions (measured on the 36-step 3x3 tiles:
+// 124.7 TF/s as is, 134.8 without the epilogue, 133.4 with the same bytes as dwordx4 stores;
+// profiles/r02_resident_workgroups_experiment.txt).  So each 32 x 32 block is transposed through a wave-private
+// LDS scratch (the operand tiles are dead after the last K step's barrier): 16 ds_write_b32 at a 40-float row stride
+// (rows r and r + 4 of the two lane halves land on disjoint bank halves), 4 ds_read_b128 giving a lane 4 consecutive
+// columns of one row, and 4 dwordx4 stores of 8 rows x 128 B each; bias / rowadd / residual are read as float4 too.
+// Per element the arithmetic and its order are unchanged (bit-identical to the scalar form, which remains for outputs
+// that cannot take aligned float4: N % 4 != 0, odd leading dimensions).
+// ------------------------------------------------------------------------------------
+
+template <int TM, int TN, int BM, int BN, int WM = 2, int WN = 2>
+__device__ __forceinline__ void store_block(const DevArgs& p, const f32x16 (&acc)[TM][TN], int row0, int col0, int wm, int wn,
+                                            int h, int l31, float* C, int ldc, const float* R, bool direct,
+                                            float* scratch = nullptr) {
+  if (scratch != nullptr && p.epi_vec) {
+    const int lane = l31 + 32 * h;
+    const int rr = lane >> 3, c4 = (lane & 7) * 4;
 #pragma unroll
-    for (int i = 0; i < S::NS; ++i) {
-      int r = row0 + S::row(i);
-      r = r < nrows ? r : nrows - 1;
-      ptr[i] = b + (long)r * ld + S::kq4();
+    for (int j = 0; j < TN; ++j) {
+      const int n = col0 + wn * (BN / WN) + j * 32 + c4;
+      const bool n_ok = n < p.N;                 // N % 4 == 0: the float4 is all inside or all outside
+      float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+      if (direct && p.bias && n_ok) {
+        const f32x4 t = ldg4(p.bias + n);
+        b0 = t[0]; b1 = t[1]; b2 = t[2]; b3 = t[3];
+      }
+#pragma unroll
+      for (int i = 0; i < TM; ++i) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) scratch[((e & 3) + 8 * (e >> 2) + 4 * h) * EPI_LD + l31] = acc[i][j][e];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int r = rr + 8 * q;
+          f32x4 v = *reinterpret_cast<const f32x4*>(scratch + r * EPI_LD + c4);
+          const int m = row0 + wm * (BM / WM) + i * 32 + r;
+          if (m >= p.M || !n_ok) continue;
+          if (direct) {
+            v = f32x4{__builtin_fmaf(v[0], p.alpha, b0), __builtin_fmaf(v[1], p.alpha, b1), __builtin_fmaf(v[2], p.alpha, b2),
+                      __builtin_fmaf(v[3], p.alpha, b3)};
+            if (p.rowadd) v += ldg4(p.rowadd + (long)p.fdRpg.div(m) * p.ld_rowadd + n);
+            if (R) v += ldg4(R + (long)m * p.ldr + n);
+          }
+          *reinterpret_cast<f32x4*>(C + (long)m * ldc + n) = v;
+        }
+      }
     }
-    off = 0;
+    return;
   }
-  __device__ __forceinline__ const float* src(int i) const { return ptr[i] + off; }
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    int n = col0 + wn * (BN / WN) + j * 32 + l31;
+    if (n >= p.N) continue;
+    float bias = (direct && p.bias) ? p.bias[n] : 0.f;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        int m = row0 + wm * (BM / WM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        if (m >= p.M) continue;
+        float v = acc[i][j][e];
+        if (direct) {
+          v = __builtin_fmaf(v, p.alpha, bias);
+          if (p.rowadd) v += p.rowadd[(long)p.fdRpg.div(m) * p.ld_rowadd + n];
+          if (R) v += R[(long)m * p.ldr + n];
+        }
+        C[(long)m * ldc + n] = v;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------
+// One K step of a (BM x BN) block on LDS tiles la / lb = 16 "pieces" of TM*TN MFMAs (4 fragment groups x 4 MFMA steps).
+// stage(piece) is the caller's staging of the NEXT step into the other buffer, issued one slot per piece from the first
+// pieces on and pinned there by sched_barrier so its address VALU runs in the shadow of the 64-cycle MFMAs; the fragments
+// of group g+1 are read during group g.
+// ------------------------------------------------------------------------------------
+template <bool KCA, bool KCB, int BM, int BN, class Stage>
+__device__ __forceinline__ void mfma_kstep(const float* la, const float* lb, f32x16 (&acc)[BM / 64][BN / 64], int wm, int wn, int h,
+                                           int l31, Stage&& stage) {
+  constexpr int TM = BM / 64, TN = BN / 64;
+  f32x4 fa[2][TM], fb[2][TN];
+#pragma unroll
+  for (int i = 0; i < TM; ++i) fa[0][i] = read_frag<KCA, BM>(la, wm * (BM / 2) + i * 32 + l31, 0, h);
+#pragma unroll
+  for (int j = 0; j < TN; ++j) fb[0][j] = read_frag<KCB, BN>(lb, wn * (BN / 2) + j * 32 + l31, 0, h);
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][i][s], fb[g & 1][j][s], acc[i][j], 0, 0, 0);
+      stage(g * 4 + s);
+      if (s == 1 && g < 3) {   // prefetch the next group's fragments into the other register set
+#pragma unroll
+        for (int i = 0; i < TM; ++i) fa[(g + 1) & 1][i] = read_frag<KCA, BM>(la, wm * (BM / 2) + i * 32 + l31, g + 1, h);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) fb[(g + 1) & 1][j] = read_frag<KCB, BN>(lb, wn * (BN / 2) + j * 32 + l31, g + 1, h);
+      }
+      // within the piece: alternate 1 MFMA with <= 7 VALU so the staging arithmetic never holds back
+      // the next MFMA by more than its 64-cycle shadow
+#pragma unroll
+      for (int q = 0; q < TM * TN; ++q) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------
+// Host side of the Winograd routes, shared by the planner (gemm_f32.hip) and the launchers (winograd.hip, wino4_fused.hip).
+// ------------------------------------------------------------------------------------
+inline FastDiv make_fastdiv(unsigned d) {
+  FastDiv f;
+  if (d == 0) d = 1;
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  f.shift = l;
+  f.mul = (unsigned)((((1ull << l) - d) << 32) / d + 1);
+  if (d == 1) f.mul = 0;
+  return f;
+}
+
+constexpr int GAD_GEMM_INTERNAL_WINO4 = 1 << 30;   // set by gad_gemm on its own batched sub-launches (names the kernel instance apart)
+struct WinoPlan {
+  int f;                     // 2: F(2x2,3x3) fused kernels; 4: F(4x4,3x3)
+  int fused4;                // f = 4: 0 = 36 batched products on the generic engine + output kernel, 1 = the six-position product kernel
+                             // (24 half-transformed panels) + output kernel, 2 = wino4_fused_kernel (products and the whole output
+                             // transform in one launch: no product ever reaches memory)
+  int bm, bn, tiles_m, tiles_n;
+  long T;                    // tiles (2x2 or 4x4 output pixels each)
+  int64_t bytes;             // scratch: V (f = 2), V + M (f = 4)
+};
+struct WinoWgradPlan {
+  long T;
+  int64_t wy_bytes, v_bytes, du_bytes, bytes;
 };
 
-// one direction of the F(4x4, 3x3) input transform: t = B^T d for the standard points {0, +-1, +-2, inf}
-//   B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
-__device__ __forceinline__ void wino4_bt(const f32x4 (&d)[6], f32x4 (&t)[6]) {
-  t[0] = 4.f * d[0] - 5.f * d[2] + d[4];
-  t[1] = -4.f * (d[1] + d[2]) + d[3] + d[4];
-  t[2] = 4.f * (d[1] - d[2]) - d[3] + d[4];
-  t[3] = 2.f * (d[3] - d[1]) - d[2] + d[4];
-  t[4] = 2.f * (d[1] - d[3]) - d[2] + d[4];
-  t[5] = 4.f * d[1] - 5.f * d[3] + d[5];
+// ---- sub-launch arguments: the size queries and the launches build them here, once ----
+// the 36 batched products of a Winograd form, C[pos] = A[pos] B[pos] (pos-major panels, no epilogue), as one launch of the
+// generic engine on its own plan (tile shapes measured within 4 % of each other here)
+inline gad_gemm_args products36(const gad_gemm_args* a, const float* A, const float* B, float* C, int am, int bm, int M, int N, int K) {
+  gad_gemm_args sub = *a;
+  sub.A = A; sub.B = B; sub.C = C;
+  sub.a_mode = am; sub.b_mode = bm;
+  sub.M = M; sub.N = N; sub.K = K;
+  sub.lda = am == GAD_A_MC ? M : K; sub.ldb = bm == GAD_B_MC ? N : K; sub.ldc = N;
+  sub.batch = 36; sub.batch_inner = 1;
+  sub.strideA0 = (int64_t)M * K; sub.strideB0 = (int64_t)N * K; sub.strideC0 = (int64_t)M * N;
+  sub.strideA1 = sub.strideB1 = sub.strideC1 = 0;
+  sub.tile_hint = 0; sub.splitk_hint = 0;
+  sub.flags = GAD_GEMM_INTERNAL_WINO4;
+  sub.B_wino = nullptr; sub.B_wino4 = nullptr; sub.wino_ws = nullptr; sub.wino_ws_bytes = 0;
+  sub.A2 = nullptr;
+  return sub;
 }
+// weight gradient: dU[pos] = Wy[pos]^T V[pos]
+inline gad_gemm_args wino_wgrad_products_args(const gad_gemm_args* a, const WinoWgradPlan& wq, float* Wy, float* V, float* dU) {
+  return products36(a, Wy, V, dU, GAD_A_MC, GAD_B_MC, a->M, a->g.C, (int)wq.T);
+}
+// three-launch F(4x4) forward: M[pos] = V[pos] U[pos]^T, then the output transform applies the epilogue
+inline gad_gemm_args wino4_products_args(const gad_gemm_args* a, const WinoPlan& wp, float* V, float* Mb) {
+  gad_gemm_args sub = products36(a, V, a->B_wino4, Mb, GAD_A_KC, GAD_B_KC, (int)wp.T, a->N, a->g.C);
+  sub.alpha = 1.f; sub.bias = nullptr; sub.rowadd = nullptr; sub.residual = nullptr;
+  return sub;
+}
+
+// winograd.hip: a = the route's canonical arguments, d = their dev_args
+int launch_wino(const gad_gemm_args* a, const WinoPlan& wp, const DevArgs& d, void* stream);
+int launch_wino_wgrad(const gad_gemm_args* a, const WinoWgradPlan& wq, void* stream);
+// wino4_fused.hip: all 36 products + the output transform, one launch
+void launch_wino4_fused(const DevArgs& w, int bm, hipStream_t st);
 
 }  // namespace gadk

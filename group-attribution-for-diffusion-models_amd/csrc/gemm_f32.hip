@@ -31,13 +31,10 @@
 //   gemm_bf16_kernel            the generic engine with bf16 operands (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
 //   conv3x3_patch_bf16_kernel   the patch convolution with bf16 operands (optionally a bf16 weight copy by LDS-DMA)
 //   splitk_reduce_kernel        deterministic reduction + fused epilogue of any split launch
+// The Winograd routes are planned here (use_wino, use_wino_wgrad) and run by winograd.hip and wino4_fused.hip.
 #include "gemm_dev.h"
 
 using namespace gadk;
-
-namespace gadk {
-void launch_wino4_fused(const DevArgs& w, int bm, hipStream_t st);   // wino4_fused.hip: all 36 products + the output transform, one launch
-}
 
 namespace {
 
@@ -630,83 +627,6 @@ struct BLoader<GAD_B_CONV, ROWS, VEC> : LoadConvCols<ROWS, VEC> {
   __device__ void setup(const DevArgs& p, const float* b, int col0, int kend) { this->init(b, p, col0, p.N, kend); }
 };
 
-// ------------------------------------------------------------------------------------
-// Epilogue shared by every contraction kernel: the wave block's accumulators (C/D map: col = lane & 31,
-// row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)) go to C with alpha, bias[n], rowadd[m / rows_per_group][n] and
-// residual[m][n] fused - or, for a split of a split-K launch (direct = false), raw to the workspace slab.
-//
-// The C/D map gives a lane ONE column and 16 rows, so stores straight from the accumulators are 64 dword wave-stores per
-// 32 x 128 block, and the epilogue's time is the count of those instructions (measured on the 36-step 3x3 tiles:
-// 124.7 TF/s as is, 134.8 without the epilogue, 133.4 with the same bytes as dwordx4 stores;
-// profiles/r02_resident_workgroups_experiment.txt).  So each 32 x 32 block is transposed through a wave-private
-// LDS scratch (the operand tiles are dead after the last K step's barrier): 16 ds_write_b32 at a 40-float row stride
-// (rows r and r + 4 of the two lane halves land on disjoint bank halves), 4 ds_read_b128 giving a lane 4 consecutive
-// columns of one row, and 4 dwordx4 stores of 8 rows x 128 B each; bias / rowadd / residual are read as float4 too.
-// Per element the arithmetic and its order are unchanged (bit-identical to the scalar form, which remains for outputs
-// that cannot take aligned float4: N % 4 != 0, odd leading dimensions).
-// ------------------------------------------------------------------------------------
-
-template <int TM, int TN, int BM, int BN, int WM = 2, int WN = 2>
-__device__ __forceinline__ void store_block(const DevArgs& p, const f32x16 (&acc)[TM][TN], int row0, int col0, int wm, int wn,
-                                            int h, int l31, float* C, int ldc, const float* R, bool direct,
-                                            float* scratch = nullptr) {
-  if (scratch != nullptr && p.epi_vec) {
-    const int lane = l31 + 32 * h;
-    const int rr = lane >> 3, c4 = (lane & 7) * 4;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int n = col0 + wn * (BN / WN) + j * 32 + c4;
-      const bool n_ok = n < p.N;                 // N % 4 == 0: the float4 is all inside or all outside
-      float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-      if (direct && p.bias && n_ok) {
-        const f32x4 t = ldg4(p.bias + n);
-        b0 = t[0]; b1 = t[1]; b2 = t[2]; b3 = t[3];
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) scratch[((e & 3) + 8 * (e >> 2) + 4 * h) * EPI_LD + l31] = acc[i][j][e];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int r = rr + 8 * q;
-          f32x4 v = *reinterpret_cast<const f32x4*>(scratch + r * EPI_LD + c4);
-          const int m = row0 + wm * (BM / WM) + i * 32 + r;
-          if (m >= p.M || !n_ok) continue;
-          if (direct) {
-            v = f32x4{__builtin_fmaf(v[0], p.alpha, b0), __builtin_fmaf(v[1], p.alpha, b1), __builtin_fmaf(v[2], p.alpha, b2),
-                      __builtin_fmaf(v[3], p.alpha, b3)};
-            if (p.rowadd) v += ldg4(p.rowadd + (long)p.fdRpg.div(m) * p.ld_rowadd + n);
-            if (R) v += ldg4(R + (long)m * p.ldr + n);
-          }
-          *reinterpret_cast<f32x4*>(C + (long)m * ldc + n) = v;
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    int n = col0 + wn * (BN / WN) + j * 32 + l31;
-    if (n >= p.N) continue;
-    float bias = (direct && p.bias) ? p.bias[n] : 0.f;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        int m = row0 + wm * (BM / WM) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (m >= p.M) continue;
-        float v = acc[i][j][e];
-        if (direct) {
-          v = __builtin_fmaf(v, p.alpha, bias);
-          if (p.rowadd) v += p.rowadd[(long)p.fdRpg.div(m) * p.ld_rowadd + n];
-          if (R) v += R[(long)m * p.ldr + n];
-        }
-        C[(long)m * ldc + n] = v;
-      }
-    }
-  }
-}
-
 
 // TAG only names an instance apart in profiles (1: the 36 batched products of the F(4x4) Winograd route)
 template <int AM, int BMODE, int BM, int BN, int VEC, int TAG = 0>
@@ -795,7 +715,8 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const DevArgs p) {
   // kt+1 (into the other buffer, last read before the previous barrier) is issued one slot per piece
   // from the first pieces on - unconditional: past the end it fetches the zero block - pinned there by
   // sched_barrier so its address VALU runs in the shadow of the 64-cycle MFMAs; the fragments of
-  // group g+1 are read during group g.
+  // group g+1 are read during group g.  (mfma_kstep of gemm_dev.h is this step; written out here because
+  // through the shared function hipcc computes the fragment addresses of every instance differently.)
   for (int kt = 0; kt < nkt; ++kt) {
     float* cur = lds + (kt & 1) * (A_TILE + B_TILE);
     float* nxt = lds + ((kt + 1) & 1) * (A_TILE + B_TILE);
@@ -1687,647 +1608,6 @@ static void launch_splitk_reduce(const DevArgs& d, int batch, hipStream_t st) {
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, d, batch);
 }
 
-// ------------------------------------------------------------------------------------
-// Winograd F(2x2, 3x3) form of the 3x3 / stride 1 / pad 1 convolution: 16 multiplies per 2x2 output tile and channel
-// pair instead of 36 (2.25x fewer MFMA FLOPs), fp32 throughout.
-//   y_tile = A^T [ sum_c U[.,.][co][c] (.) V[.,.][tile][c] ] A,   U = G w G^T (per weight version, wino_weights_kernel),
-//   V = B^T d B (per launch, wino_input_kernel),   B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 1 0 -1],
-//   G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1],   A^T = [1 1 1 0; 0 1 -1 -1]           (Lavin & Gray 2016, standard points).
-// wino_gemm_kernel runs the 16 per-position products [tiles x Cin] x [Cin x Cout] of one (64 tiles x 128 channels) or
-// (128 x 64) block back to back as ONE K loop of 16 Cin/32 steps on the lean dense loaders (V and U are k-contiguous
-// rows: LDS-DMA, no masks); after the last step of a position the 32-register product block is folded into the four
-// output-pixel accumulators with the position's A^T (x) A^T coefficient (+1 / 0 / -1: exact), so M = U (.) V never
-// exists in memory, and the shared float4 epilogue (bias, time-embedding row, residual) writes the four pixels of
-// every tile.  Transforms add a rounding per add (the input transform has unit coefficients, the weight transform
-// halves): the result differs from the direct kernels' by fp32 reassociation noise of a few ulp of the accumulated
-// magnitude, not bit for bit.
-// ------------------------------------------------------------------------------------
-struct WinoIn {
-  const float* x;
-  float* V;
-  int H, W, C, ldx, up;      // source map H x W (before the fused nearest-2x upsample when up = 1), C channels
-  int TH, TW;                // tiles per image = (He / 2) x (We / 2)
-  long T;                    // B * TH * TW
-};
-
-__global__ __launch_bounds__(256) void wino_input_kernel(const WinoIn p) {
-  const int C4 = p.C >> 2;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.T * C4) return;
-  const long tile = idx / C4;
-  const int c = (int)(idx - tile * C4) * 4;
-  const int per = p.TH * p.TW;
-  const int n = (int)(tile / per);
-  const int r = (int)(tile - (long)n * per);
-  const int ty = r / p.TW, tx = r - ty * p.TW;
-  const int He = p.H << p.up, We = p.W << p.up;
-  const float* img = p.x + (long)n * p.H * p.W * p.ldx + c;
-  f32x4 t[4][4];
-#pragma unroll
-  for (int dx = 0; dx < 4; ++dx) {
-    const int xx = 2 * tx - 1 + dx;
-    const bool xok = xx >= 0 && xx < We;
-    f32x4 d[4];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy) {
-      const int yy = 2 * ty - 1 + dy;
-      const bool ok = xok && yy >= 0 && yy < He;
-      d[dy] = ok ? ldg4(img + ((long)(yy >> p.up) * p.W + (xx >> p.up)) * p.ldx) : zero4();
-    }
-    t[0][dx] = d[0] - d[2];
-    t[1][dx] = d[1] + d[2];
-    t[2][dx] = d[2] - d[1];
-    t[3][dx] = d[1] - d[3];
-  }
-  const long pos_stride = p.T * p.C;
-  float* out = p.V + tile * p.C + c;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    *reinterpret_cast<f32x4*>(out + (long)(4 * i + 0) * pos_stride) = t[i][0] - t[i][2];
-    *reinterpret_cast<f32x4*>(out + (long)(4 * i + 1) * pos_stride) = t[i][1] + t[i][2];
-    *reinterpret_cast<f32x4*>(out + (long)(4 * i + 2) * pos_stride) = t[i][2] - t[i][1];
-    *reinterpret_cast<f32x4*>(out + (long)(4 * i + 3) * pos_stride) = t[i][1] - t[i][3];
-  }
-}
-
-// U[pos][co][ci] = (G w G^T)[pos] for 32 x 32 (co, ci) tiles of the 3x3 weights listed in `table`
-// (rows {src offset, dst offset, Cout, Cin, co0, ci0} in floats; src storage [Cout][3][3][Cin])
-__global__ __launch_bounds__(256) void wino_weights_kernel(const float* src, float* dst, const long* table) {
-  const long* row = table + 6 * (long)blockIdx.x;
-  const long soff = row[0], doff = row[1];
-  const int Cout = (int)row[2], Cin = (int)row[3], co0 = (int)row[4], ci0 = (int)row[5];
-  const int ci = ci0 + (threadIdx.x & 31);
-  if (ci >= Cin) return;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int co = co0 + (threadIdx.x >> 5) + 8 * q;
-    if (co >= Cout) continue;
-    const float* w = src + soff + (long)co * 9 * Cin + ci;
-    float g[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int s = 0; s < 3; ++s) g[r][s] = w[(long)(r * 3 + s) * Cin];
-    float gg[4][3];                       // G g
-#pragma unroll
-    for (int s = 0; s < 3; ++s) {
-      gg[0][s] = g[0][s];
-      gg[1][s] = 0.5f * (g[0][s] + g[1][s] + g[2][s]);
-      gg[2][s] = 0.5f * (g[0][s] - g[1][s] + g[2][s]);
-      gg[3][s] = g[2][s];
-    }
-    float* u = dst + doff + (long)co * Cin + ci;
-    const long ps = (long)Cout * Cin;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      u[(long)(4 * i + 0) * ps] = gg[i][0];
-      u[(long)(4 * i + 1) * ps] = 0.5f * (gg[i][0] + gg[i][1] + gg[i][2]);
-      u[(long)(4 * i + 2) * ps] = 0.5f * (gg[i][0] - gg[i][1] + gg[i][2]);
-      u[(long)(4 * i + 3) * ps] = gg[i][2];
-    }
-  }
-}
-
-
-// one output pixel (di, dj) of every 2x2 tile of the block: p.M counts TILES, p.fdHoWo / p.fdWo divide by the tiles per
-// image / per tile row, the pixel row is ((n Ho + 2 ty + di) Wo + 2 tx + dj); same arithmetic order as store_block
-template <int TM, int TN, int BM, int BN>
-__device__ __forceinline__ void store_block_wino(const DevArgs& p, const f32x16 (&acc)[TM][TN], int row0, int col0, int wm, int wn,
-                                                 int h, int l31, int di, int dj, float* scratch) {
-  const int lane = l31 + 32 * h;
-  const int rr = lane >> 3, c4 = (lane & 7) * 4;
-  const int tiles_img = (p.g.Ho >> 1) * (p.g.Wo >> 1), TW = p.g.Wo >> 1;
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int n = col0 + wn * (BN / 2) + j * 32 + c4;
-    const bool n_ok = n < p.N;
-    float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-    if (p.bias && n_ok) {
-      const f32x4 t = ldg4(p.bias + n);
-      b0 = t[0]; b1 = t[1]; b2 = t[2]; b3 = t[3];
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) scratch[((e & 3) + 8 * (e >> 2) + 4 * h) * EPI_LD + l31] = acc[i][j][e];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int r = rr + 8 * q;
-        f32x4 v = *reinterpret_cast<const f32x4*>(scratch + r * EPI_LD + c4);
-        const int m = row0 + wm * (BM / 2) + i * 32 + r;
-        if (m >= p.M || !n_ok) continue;
-        const int img = p.fdHoWo.div(m), rem = m - img * tiles_img;
-        const int ty = p.fdWo.div(rem), tx = rem - ty * TW;
-        const long pix = ((long)img * p.g.Ho + 2 * ty + di) * p.g.Wo + 2 * tx + dj;
-        v = f32x4{__builtin_fmaf(v[0], p.alpha, b0), __builtin_fmaf(v[1], p.alpha, b1), __builtin_fmaf(v[2], p.alpha, b2),
-                  __builtin_fmaf(v[3], p.alpha, b3)};
-        if (p.rowadd) v += ldg4(p.rowadd + (long)img * p.ld_rowadd + n);
-        if (p.residual) v += ldg4(p.residual + pix * p.ldr + n);
-        *reinterpret_cast<f32x4*>(p.C + pix * p.ldc + n) = v;
-      }
-    }
-  }
-}
-
-// p.A = V [16][T][Cin] (p.sA0 = T Cin), p.B = U [16][Cout][Cin] (p.sB0 = Cout Cin), p.M = T tiles, p.N = Cout, p.K = Cin
-template <int BM, int BN>
-__global__ __launch_bounds__(NTHREADS, 2) void wino_gemm_kernel(const DevArgs p) {
-  constexpr int TM = BM / 64, TN = BN / 64;
-  using AL = WinoKC<BM>;
-  using BL = WinoKC<BN>;
-  constexpr int A_TILE = BK * BM;
-  constexpr int B_TILE = BK * BN;
-  __shared__ __attribute__((aligned(16))) float lds[2 * (A_TILE + B_TILE)];
-
-  const int t = xcd_remap(blockIdx.x, gridDim.x);
-  const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
-  const int row0 = tile_m * BM, col0 = tile_n * BN;
-  const int kc = p.K / BK;                       // K steps per position
-  const int nsteps = 16 * kc;
-
-  AL al;
-  BL bl;
-  al.init(p.A, p.lda, row0, p.M);
-  bl.init(p.B, p.ldb, col0, p.N);
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, l31 = lane & 31;
-
-  f32x16 acc[TM][TN], Y[4][TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        acc[i][j][e] = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Y[q][i][j][e] = 0.f;
-      }
-
-  auto stage_slot = [&](int piece, float* ta, float* tb) {
-    constexpr int NSA = AL::NS, NSB = BL::NS;
-    if (piece < NSA) glds16(al.src(piece), AL::dma_dst(ta, piece));
-    else if (piece < NSA + NSB) glds16(bl.src(piece - NSA), BL::dma_dst(tb, piece - NSA));
-  };
-#pragma unroll
-  for (int q = 0; q < AL::NS + BL::NS; ++q) stage_slot(q, lds, lds + A_TILE);
-  barrier_after_dma();
-
-  int pos = 0, kk = 0;                           // position and K step of the step being multiplied
-  for (int s = 0; s < nsteps; ++s) {
-    float* cur = lds + (s & 1) * (A_TILE + B_TILE);
-    float* nxt = lds + ((s + 1) & 1) * (A_TILE + B_TILE);
-    const float* la = cur;
-    const float* lb = cur + A_TILE;
-    {                                            // offsets of step s + 1 (the step past the end re-reads the last one)
-      int pn = pos, kn = kk + 1;
-      if (kn == kc) { kn = 0; ++pn; }
-      if (pn == 16) { pn = 15; kn = kc - 1; }
-      al.off = (long)pn * p.sA0 + kn * BK;
-      bl.off = (long)pn * p.sB0 + kn * BK;
-    }
-    f32x4 fa[2][TM], fb[2][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[0][i] = read_frag<true, BM>(la, wm * (BM / 2) + i * 32 + l31, 0, h);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) fb[0][j] = read_frag<true, BN>(lb, wn * (BN / 2) + j * 32 + l31, 0, h);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][i][q4], fb[g & 1][j][q4], acc[i][j], 0, 0, 0);
-        stage_slot(g * 4 + q4, nxt, nxt + A_TILE);
-        if (q4 == 1 && g < 3) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) fa[(g + 1) & 1][i] = read_frag<true, BM>(la, wm * (BM / 2) + i * 32 + l31, g + 1, h);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) fb[(g + 1) & 1][j] = read_frag<true, BN>(lb, wn * (BN / 2) + j * 32 + l31, g + 1, h);
-        }
-#pragma unroll
-        for (int q = 0; q < TM * TN; ++q) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (++kk == kc) {                            // position done: fold its product block into the four output pixels
-      const int xi = pos >> 2, nu = pos & 3;
-      const float r0 = xi < 3 ? 1.f : 0.f, r1 = xi == 0 ? 0.f : (xi == 1 ? 1.f : -1.f);
-      const float c0 = nu < 3 ? 1.f : 0.f, c1 = nu == 0 ? 0.f : (nu == 1 ? 1.f : -1.f);
-      const float w00 = r0 * c0, w01 = r0 * c1, w10 = r1 * c0, w11 = r1 * c1;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const float a = acc[i][j][e];
-            Y[0][i][j][e] = __builtin_fmaf(w00, a, Y[0][i][j][e]);
-            Y[1][i][j][e] = __builtin_fmaf(w01, a, Y[1][i][j][e]);
-            Y[2][i][j][e] = __builtin_fmaf(w10, a, Y[2][i][j][e]);
-            Y[3][i][j][e] = __builtin_fmaf(w11, a, Y[3][i][j][e]);
-            acc[i][j][e] = 0.f;
-          }
-      kk = 0;
-      ++pos;
-    }
-    barrier_after_dma();
-  }
-
-  float* scratch = lds + (tid >> 6) * EPI_WAVE;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) store_block_wino<TM, TN, BM, BN>(p, Y[q], row0, col0, wm, wn, h, l31, q >> 1, q & 1, scratch);
-}
-
-// F(4x4, 3x3) products with the output transform's nu direction folded in: block (xi, tile_m, tile_n) runs the SIX products
-// M[xi][nu] = V[6 xi + nu] U[6 xi + nu]^T of its tile back to back as one K loop and folds each finished product block into four
-// accumulators with A^T's column nu ([1 0 0 0], [1 1 1 1], [1 -1 1 -1], [1 2 4 8], [1 -2 4 -8], [0 0 0 1]), then stores
-// Mh[4 xi + j][tile][n] raw: 24 values per tile and channel reach memory instead of 36, one pipeline prologue serves six products.
-// p.A = V [36][T][Cin] (p.sA0 = T Cin), p.B = U [36][Cout][Cin] (p.sB0 = Cout Cin), p.C = Mh [24][T][Cout] (p.sC0 = T Cout), p.M = T, p.N = Cout, p.K = Cin
-template <int BM, int BN>
-__global__ __launch_bounds__(NTHREADS, 2) void wino4_gemm_kernel(const DevArgs p) {
-  constexpr int TM = BM / 64, TN = BN / 64;
-  using AL = WinoKC<BM>;
-  using BL = WinoKC<BN>;
-  constexpr int A_TILE = BK * BM;
-  constexpr int B_TILE = BK * BN;
-  __shared__ __attribute__((aligned(16))) float lds[2 * (A_TILE + B_TILE)];
-
-  const int t0 = xcd_remap(blockIdx.x, gridDim.x);
-  const int per_xi = p.tiles_m * p.tiles_n;
-  const int xi6 = t0 / per_xi, t = t0 - xi6 * per_xi;          // xi slowest: neighbouring blocks share the V rows / U panel
-  const int tile_m = t / p.tiles_n, tile_n = t - tile_m * p.tiles_n;
-  const int row0 = tile_m * BM, col0 = tile_n * BN;
-  const int kc = p.K / BK;                       // K steps per position
-  const int nsteps = 6 * kc;
-  const int pos0 = 6 * xi6;
-
-  AL al;
-  BL bl;
-  al.init(p.A, p.lda, row0, p.M);
-  bl.init(p.B, p.ldb, col0, p.N);
-  al.off = (long)pos0 * p.sA0;
-  bl.off = (long)pos0 * p.sB0;
-
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wm = wave >> 1, wn = wave & 1, h = lane >> 5, l31 = lane & 31;
-
-  f32x16 acc[TM][TN], Y[4][TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        acc[i][j][e] = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) Y[q][i][j][e] = 0.f;
-      }
-
-  auto stage_slot = [&](int piece, float* ta, float* tb) {
-    constexpr int NSA = AL::NS, NSB = BL::NS;
-    if (piece < NSA) glds16(al.src(piece), AL::dma_dst(ta, piece));
-    else if (piece < NSA + NSB) glds16(bl.src(piece - NSA), BL::dma_dst(tb, piece - NSA));
-  };
-#pragma unroll
-  for (int q = 0; q < AL::NS + BL::NS; ++q) stage_slot(q, lds, lds + A_TILE);
-  barrier_after_dma();
-
-  int pos = 0, kk = 0;                           // position and K step of the step being multiplied
-  for (int s = 0; s < nsteps; ++s) {
-    float* cur = lds + (s & 1) * (A_TILE + B_TILE);
-    float* nxt = lds + ((s + 1) & 1) * (A_TILE + B_TILE);
-    const float* la = cur;
-    const float* lb = cur + A_TILE;
-    {                                            // offsets of step s + 1 (the step past the end re-reads the last one)
-      int pn = pos, kn = kk + 1;
-      if (kn == kc) { kn = 0; ++pn; }
-      if (pn == 6) { pn = 5; kn = kc - 1; }
-      al.off = (long)(pos0 + pn) * p.sA0 + kn * BK;
-      bl.off = (long)(pos0 + pn) * p.sB0 + kn * BK;
-    }
-    f32x4 fa[2][TM], fb[2][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) fa[0][i] = read_frag<true, BM>(la, wm * (BM / 2) + i * 32 + l31, 0, h);
-#pragma unroll
-    for (int j = 0; j < TN; ++j) fb[0][j] = read_frag<true, BN>(lb, wn * (BN / 2) + j * 32 + l31, 0, h);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][i][q4], fb[g & 1][j][q4], acc[i][j], 0, 0, 0);
-        stage_slot(g * 4 + q4, nxt, nxt + A_TILE);
-        if (q4 == 1 && g < 3) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) fa[(g + 1) & 1][i] = read_frag<true, BM>(la, wm * (BM / 2) + i * 32 + l31, g + 1, h);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) fb[(g + 1) & 1][j] = read_frag<true, BN>(lb, wn * (BN / 2) + j * 32 + l31, g + 1, h);
-        }
-#pragma unroll
-        for (int q = 0; q < TM * TN; ++q) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    if (++kk == kc) {                            // position done: fold its product block into the four output pixels
-      // A^T column of nu = pos: [1 0 0 0], [1 1 1 1], [1 -1 1 -1], [1 2 4 8], [1 -2 4 -8], [0 0 0 1]
-      const float sg = (pos == 2 || pos == 4) ? -1.f : 1.f, two = pos >= 3 ? 2.f : 1.f;
-      const float w00 = pos == 5 ? 0.f : 1.f;
-      const float w01 = (pos == 0 || pos == 5) ? 0.f : sg * two;
-      const float w10 = (pos == 0 || pos == 5) ? 0.f : two * two;
-      const float w11 = pos == 0 ? 0.f : (pos == 5 ? 1.f : sg * two * two * two);
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const float a = acc[i][j][e];
-            Y[0][i][j][e] = __builtin_fmaf(w00, a, Y[0][i][j][e]);
-            Y[1][i][j][e] = __builtin_fmaf(w01, a, Y[1][i][j][e]);
-            Y[2][i][j][e] = __builtin_fmaf(w10, a, Y[2][i][j][e]);
-            Y[3][i][j][e] = __builtin_fmaf(w11, a, Y[3][i][j][e]);
-            acc[i][j][e] = 0.f;
-          }
-      kk = 0;
-      ++pos;
-    }
-    barrier_after_dma();
-  }
-
-  float* scratch = lds + (tid >> 6) * EPI_WAVE;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    store_block<TM, TN, BM, BN>(p, Y[q], row0, col0, wm, wn, h, l31, p.C + (long)(4 * xi6 + q) * p.sC0, p.N, nullptr, false, scratch);
-}
-
-// ------------------------------------------------------------------------------------
-// Winograd F(4x4, 3x3): 36 multiplies per 4x4 output tile and channel pair instead of 144 (4x fewer MFMA FLOPs) and a
-// transformed input of only 2.25x the input.  Sixteen output-pixel accumulator sets do not fit a wave, so the element-wise
-// products M[36][tiles][Cout] go through memory: wino4_input_kernel (V = B^T d B, 6x6 patches), the generic engine as ONE
-// batched launch of 36 [tiles x Cin] x [Cin x Cout] products on its 128 x 128 lean tiles, wino4_output_kernel (y = A^T M A
-// + the fused epilogue).  Standard points {0, +-1, +-2, inf}:
-//   B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1]
-//   G   = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]
-//   A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1]
-// fp32 throughout; the larger transform coefficients cost about a decimal digit against the direct kernels (measured
-// max error 4e-6 of the output scale vs 4e-7), still an order of magnitude inside the contraction tolerance of the tests.
-// ------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(256) void wino4_input_kernel(const WinoIn p) {   // p.TH / p.TW / p.T count 4x4 tiles
-  const int C4 = p.C >> 2;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.T * C4) return;
-  const long tile = idx / C4;
-  const int c = (int)(idx - tile * C4) * 4;
-  const int per = p.TH * p.TW;
-  const int n = (int)(tile / per);
-  const int r = (int)(tile - (long)n * per);
-  const int ty = r / p.TW, tx = r - ty * p.TW;
-  const int He = p.H << p.up, We = p.W << p.up;
-  const float* img = p.x + (long)n * p.H * p.W * p.ldx + c;
-  f32x4 t[6][6];                                 // t[i][dx] = (B^T d)[i][dx]
-#pragma unroll
-  for (int dx = 0; dx < 6; ++dx) {
-    const int xx = 4 * tx - 1 + dx;
-    const bool xok = xx >= 0 && xx < We;
-    f32x4 d[6], col[6];
-#pragma unroll
-    for (int dy = 0; dy < 6; ++dy) {
-      const int yy = 4 * ty - 1 + dy;
-      const bool ok = xok && yy >= 0 && yy < He;
-      d[dy] = ok ? ldg4(img + ((long)(yy >> p.up) * p.W + (xx >> p.up)) * p.ldx) : zero4();
-    }
-    wino4_bt(d, col);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) t[i][dx] = col[i];
-  }
-  const long pos_stride = p.T * p.C;
-  float* out = p.V + tile * p.C + c;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    f32x4 v[6];
-    wino4_bt(t[i], v);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) *reinterpret_cast<f32x4*>(out + (long)(6 * i + j) * pos_stride) = v[j];
-  }
-}
-
-// U[36][co][ci] = G w G^T, 32 x 32 (co, ci) tiles as in wino_weights_kernel (dst region of 36 Cout Cin floats per weight)
-__global__ __launch_bounds__(256) void wino4_weights_kernel(const float* src, float* dst, const long* table) {
-  const long* row = table + 6 * (long)blockIdx.x;
-  const long soff = row[0], doff = row[1];
-  const int Cout = (int)row[2], Cin = (int)row[3], co0 = (int)row[4], ci0 = (int)row[5];
-  const int ci = ci0 + (threadIdx.x & 31);
-  if (ci >= Cin) return;
-  auto gmul = [](float a, float b, float c, float (&o)[6]) {      // G [a b c]^T
-    o[0] = 0.25f * a;
-    o[1] = (-1.f / 6.f) * (a + b + c);
-    o[2] = (-1.f / 6.f) * (a - b + c);
-    o[3] = (1.f / 24.f) * a + (1.f / 12.f) * b + (1.f / 6.f) * c;
-    o[4] = (1.f / 24.f) * a - (1.f / 12.f) * b + (1.f / 6.f) * c;
-    o[5] = c;
-  };
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int co = co0 + (threadIdx.x >> 5) + 8 * q;
-    if (co >= Cout) continue;
-    const float* w = src + soff + (long)co * 9 * Cin + ci;
-    float gg[6][3];                               // G g (columns s = 0..2)
-#pragma unroll
-    for (int sx = 0; sx < 3; ++sx) {
-      float o[6];
-      gmul(w[(long)(0 * 3 + sx) * Cin], w[(long)(1 * 3 + sx) * Cin], w[(long)(2 * 3 + sx) * Cin], o);
-#pragma unroll
-      for (int i = 0; i < 6; ++i) gg[i][sx] = o[i];
-    }
-    float* u = dst + doff + (long)co * Cin + ci;
-    const long ps = (long)Cout * Cin;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      float o[6];
-      gmul(gg[i][0], gg[i][1], gg[i][2], o);
-#pragma unroll
-      for (int j = 0; j < 6; ++j) u[(long)(6 * i + j) * ps] = o[j];
-    }
-  }
-}
-
-struct WinoOut {
-  const float* Mb;           // [36][T][N]
-  float* y;
-  const float* bias;
-  const float* rowadd;
-  const float* residual;
-  int N, ldc, ldr, ld_rowadd, Ho, Wo, TH, TW;
-  long T;
-  float alpha;
-};
-
-__device__ __forceinline__ void wino4_at(const f32x4 (&m)[6], f32x4 (&y)[4]) {
-  const f32x4 s12 = m[1] + m[2], d12 = m[1] - m[2], s34 = m[3] + m[4], d34 = m[3] - m[4];
-  y[0] = m[0] + s12 + s34;
-  y[1] = d12 + 2.f * d34;
-  y[2] = s12 + 4.f * s34;
-  y[3] = d12 + 8.f * d34 + m[5];
-}
-
-// half = true: Mb holds the 24 half-transformed panels Mh[4 xi + j] of wino4_gemm_kernel (nu direction already folded)
-template <bool HALF>
-__global__ __launch_bounds__(256) void wino4_output_kernel(const WinoOut p) {
-  const int N4 = p.N >> 2;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.T * N4) return;
-  const long tile = idx / N4;
-  const int n = (int)(idx - tile * N4) * 4;
-  const int per = p.TH * p.TW;
-  const int img = (int)(tile / per);
-  const int r = (int)(tile - (long)img * per);
-  const int ty = r / p.TW, tx = r - ty * p.TW;
-  const long pos_stride = p.T * p.N;
-  const float* src = p.Mb + tile * p.N + n;
-  f32x4 t[4][HALF ? 4 : 6];                      // t[i][nu] = (A^T M)[i][nu]   (HALF: t[i][j] = y[i][j] already)
-#pragma unroll
-  for (int nu = 0; nu < (HALF ? 4 : 6); ++nu) {
-    f32x4 m[6], col[4];
-#pragma unroll
-    for (int xi = 0; xi < 6; ++xi) m[xi] = ldg4(src + (long)((HALF ? 4 : 6) * xi + nu) * pos_stride);
-    wino4_at(m, col);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) t[i][nu] = col[i];
-  }
-  const f32x4 b = p.bias ? ldg4(p.bias + n) : zero4();
-  const f32x4 ra = p.rowadd ? ldg4(p.rowadd + (long)img * p.ld_rowadd + n) : zero4();
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f32x4 y[4];
-    if constexpr (HALF) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) y[j] = t[i][j];
-    } else {
-      f32x4 row6[6];
-#pragma unroll
-      for (int j = 0; j < 6; ++j) row6[j] = t[i][HALF ? 0 : j];
-      wino4_at(row6, y);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const long pix = ((long)img * p.Ho + 4 * ty + i) * p.Wo + 4 * tx + j;
-      f32x4 v = f32x4{__builtin_fmaf(y[j][0], p.alpha, b[0]), __builtin_fmaf(y[j][1], p.alpha, b[1]),
-                      __builtin_fmaf(y[j][2], p.alpha, b[2]), __builtin_fmaf(y[j][3], p.alpha, b[3])};
-      if (p.rowadd) v += ra;
-      if (p.residual) v += ldg4(p.residual + pix * p.ldr + n);
-      *reinterpret_cast<f32x4*>(p.y + pix * p.ldc + n) = v;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// Weight gradient of the same convolutions in F(4x4, 3x3) form (the transposed algorithm):
-//   dW = G^T [ sum_tiles (A dy A^T) (.) (B^T x B) ] G        per (co, ci)
-// wino4_dy_kernel transforms the 4x4 output-gradient tiles (A = (A^T)^T, 6 x 4), wino4_input_kernel the 6x6 input patches as
-// in the forward pass, the generic engine runs the 36 products [Cout x tiles] x [tiles x Cin] (K = tiles: long, split) as one
-// batched launch, wino4_dw_kernel applies G^T . G and writes the [Cout][3][3][Cin] gradient.  36 multiplies per tile and
-// channel pair instead of 144.
-// ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void wino4_dy_kernel(const WinoIn p) {      // p.x = dy [B][H][W][C], p.V = Wy [36][T][C]
-  const int C4 = p.C >> 2;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= p.T * C4) return;
-  const long tile = idx / C4;
-  const int c = (int)(idx - tile * C4) * 4;
-  const int per = p.TH * p.TW;
-  const int n = (int)(tile / per);
-  const int r = (int)(tile - (long)n * per);
-  const int ty = r / p.TW, tx = r - ty * p.TW;
-  const float* img = p.x + ((long)n * p.H * p.W + (long)(4 * ty) * p.W + 4 * tx) * p.ldx + c;
-  auto amul = [](const f32x4 (&d)[4], f32x4 (&t)[6]) {        // A d: [1 0 0 0; 1 1 1 1; 1 -1 1 -1; 1 2 4 8; 1 -2 4 -8; 0 0 0 1]
-    const f32x4 s02 = d[0] + d[2], s13 = d[1] + d[3], a = d[0] + 4.f * d[2], b = 2.f * d[1] + 8.f * d[3];
-    t[0] = d[0];
-    t[1] = s02 + s13;
-    t[2] = s02 - s13;
-    t[3] = a + b;
-    t[4] = a - b;
-    t[5] = d[3];
-  };
-  f32x4 t[6][4];                                 // t[i][dx] = (A d)[i][dx]
-#pragma unroll
-  for (int dx = 0; dx < 4; ++dx) {
-    f32x4 d[4], col[6];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy) d[dy] = ldg4(img + ((long)dy * p.W + dx) * p.ldx);
-    amul(d, col);
-#pragma unroll
-    for (int i = 0; i < 6; ++i) t[i][dx] = col[i];
-  }
-  const long pos_stride = p.T * p.C;
-  float* out = p.V + tile * p.C + c;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    f32x4 v[6];
-    amul(t[i], v);
-#pragma unroll
-    for (int j = 0; j < 6; ++j) *reinterpret_cast<f32x4*>(out + (long)(6 * i + j) * pos_stride) = v[j];
-  }
-}
-
-// dW[co][r][s][ci] = (G^T dU G)[r][s] from dU [36][Cout][Cin]; one thread per (co, 4 ci)
-__global__ __launch_bounds__(256) void wino4_dw_kernel(const float* dU, float* dW, int Cout, int Cin, int ldc) {
-  const int C4 = Cin >> 2;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (long)Cout * C4) return;
-  const int co = (int)(idx / C4), ci = (int)(idx - (long)co * C4) * 4;
-  const long ps = (long)Cout * Cin;
-  const float* src = dU + (long)co * Cin + ci;
-  auto gt = [](const f32x4 (&m)[6], f32x4 (&o)[3]) {          // G^T m
-    const f32x4 s12 = m[1] + m[2], d21 = m[2] - m[1], s34 = m[3] + m[4], d34 = m[3] - m[4];
-    o[0] = 0.25f * m[0] - (1.f / 6.f) * s12 + (1.f / 24.f) * s34;
-    o[1] = (1.f / 6.f) * d21 + (1.f / 12.f) * d34;
-    o[2] = (1.f / 6.f) * (s34 - s12) + m[5];
-  };
-  f32x4 t[3][6];                                 // t[r][nu] = (G^T dU)[r][nu]
-#pragma unroll
-  for (int nu = 0; nu < 6; ++nu) {
-    f32x4 m[6], col[3];
-#pragma unroll
-    for (int xi = 0; xi < 6; ++xi) m[xi] = ldg4(src + (long)(6 * xi + nu) * ps);
-    gt(m, col);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) t[r][nu] = col[r];
-  }
-  float* dst = dW + (long)co * ldc + ci;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    f32x4 o[3];
-    gt(t[r], o);
-#pragma unroll
-    for (int sx = 0; sx < 3; ++sx) *reinterpret_cast<f32x4*>(dst + (long)(r * 3 + sx) * Cin) = o[sx];
-  }
-}
-
-static FastDiv make_fastdiv(unsigned d) {
-  FastDiv f;
-  if (d == 0) d = 1;
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;
-  f.shift = l;
-  f.mul = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-  if (d == 1) f.mul = 0;
-  return f;
-}
-
 static int pick_vec(const gad_gemm_args* a) {
   int vec = 4;
   const int am = a->a_mode, bmode = a->b_mode;
@@ -2695,16 +1975,6 @@ static gad_gemm_args canonical(const gad_gemm_args* a) {
 // Winograd F(2x2, 3x3) route of the fp32 3x3 / stride 1 / pad 1 forward convolution (and, through ops.dgrad_as_forward, of
 // its data gradient): taken when the caller supplies the transformed weights (B_wino) and the launch has tiles enough to
 // fill the chip - small maps at small batch keep the direct LDS-patch kernels and their split-K.
-constexpr int GAD_GEMM_INTERNAL_WINO4 = 1 << 30;   // set by gad_gemm on its own batched sub-launches (names the kernel instance apart)
-struct WinoPlan {
-  int f;                     // 2: F(2x2,3x3) fused kernels; 4: F(4x4,3x3)
-  int fused4;                // f = 4: 0 = 36 batched products on the generic engine + output kernel, 1 = the six-position product kernel
-                             // (24 half-transformed panels) + output kernel, 2 = wino4_fused_kernel (products and the whole output
-                             // transform in one launch: no product ever reaches memory)
-  int bm, bn, tiles_m, tiles_n;
-  long T;                    // tiles (2x2 or 4x4 output pixels each)
-  int64_t bytes;             // scratch: V (f = 2), V + M (f = 4)
-};
 static bool use_wino(const gad_gemm_args* a, WinoPlan* wp) {
   const gad_conv_geom& g = a->g;
   if ((!a->B_wino && !a->B_wino4) || a->operand_precision != 0 || a->a_mode != GAD_A_CONV || a->b_mode != GAD_B_KC || a->A2 || a->A_k2) return false;
@@ -2801,10 +2071,6 @@ static bool use_wino(const gad_gemm_args* a, WinoPlan* wp) {
 
 // Winograd F(4x4, 3x3) weight gradient: opted into by the caller (GAD_GEMM_WINO_WGRAD + wino_ws), taken when it models >= 10 %
 // faster than the direct kernels (transform bytes at 4.9 TB/s + the 36 batched products at ~100 TF/s + three small launches)
-struct WinoWgradPlan {
-  long T;
-  int64_t wy_bytes, v_bytes, du_bytes, bytes;
-};
 static bool use_wino_wgrad(const gad_gemm_args* a, WinoWgradPlan* wq) {
   const gad_conv_geom& g = a->g;
   if (!(a->flags & GAD_GEMM_WINO_WGRAD) || (a->flags & (GAD_GEMM_NO_WINO | GAD_GEMM_NO_PATCH | GAD_GEMM_INTERNAL_WINO4))) return false;
@@ -2825,36 +2091,6 @@ static bool use_wino_wgrad(const gad_gemm_args* a, WinoWgradPlan* wq) {
                      3.0 * (double)wq->du_bytes / 3.0e12 + 30e-6;
   const double t_direct = 2.0 * a->K * (double)a->M * a->N / 115e12;
   return t_w < 0.9 * t_direct;
-}
-
-// ---- sub-launch arguments: the size queries and the launches build them here, once ----
-
-// the 36 batched products of a Winograd form, C[pos] = A[pos] B[pos] (pos-major panels, no epilogue), as one launch of the
-// generic engine on its own plan (tile shapes measured within 4 % of each other here)
-static gad_gemm_args products36(const gad_gemm_args* a, const float* A, const float* B, float* C, int am, int bm, int M, int N, int K) {
-  gad_gemm_args sub = *a;
-  sub.A = A; sub.B = B; sub.C = C;
-  sub.a_mode = am; sub.b_mode = bm;
-  sub.M = M; sub.N = N; sub.K = K;
-  sub.lda = am == GAD_A_MC ? M : K; sub.ldb = bm == GAD_B_MC ? N : K; sub.ldc = N;
-  sub.batch = 36; sub.batch_inner = 1;
-  sub.strideA0 = (int64_t)M * K; sub.strideB0 = (int64_t)N * K; sub.strideC0 = (int64_t)M * N;
-  sub.strideA1 = sub.strideB1 = sub.strideC1 = 0;
-  sub.tile_hint = 0; sub.splitk_hint = 0;
-  sub.flags = GAD_GEMM_INTERNAL_WINO4;
-  sub.B_wino = nullptr; sub.B_wino4 = nullptr; sub.wino_ws = nullptr; sub.wino_ws_bytes = 0;
-  sub.A2 = nullptr;
-  return sub;
-}
-// weight gradient: dU[pos] = Wy[pos]^T V[pos]
-static gad_gemm_args wino_wgrad_products_args(const gad_gemm_args* a, const WinoWgradPlan& wq, float* Wy, float* V, float* dU) {
-  return products36(a, Wy, V, dU, GAD_A_MC, GAD_B_MC, a->M, a->g.C, (int)wq.T);
-}
-// three-launch F(4x4) forward: M[pos] = V[pos] U[pos]^T, then the output transform applies the epilogue
-static gad_gemm_args wino4_products_args(const gad_gemm_args* a, const WinoPlan& wp, float* V, float* Mb) {
-  gad_gemm_args sub = products36(a, V, a->B_wino4, Mb, GAD_A_KC, GAD_B_KC, (int)wp.T, a->N, a->g.C);
-  sub.alpha = 1.f; sub.bias = nullptr; sub.rowadd = nullptr; sub.residual = nullptr;
-  return sub;
 }
 
 // ---- the route: which kernels run a launch, and on what plan ----
@@ -2989,21 +2225,6 @@ extern "C" int64_t gad_gemm_wino_bytes(const gad_gemm_args* a) {
 
 extern "C" int64_t gad_gemm_workspace_bytes(const gad_gemm_args* a) { return a ? workspace_bytes(route_of(a)) : 0; }
 
-extern "C" int gad_wino_weights(const float* src, float* dst, const int64_t* table, int64_t n_tiles, void* stream) {
-  GAD_CHECK(src && dst && table && n_tiles > 0 && n_tiles < (1L << 31), "gad_wino_weights: bad arguments");
-  static_assert(sizeof(long) == sizeof(int64_t), "table rows are 64-bit");
-  hipLaunchKernelGGL(wino_weights_kernel, dim3((unsigned)n_tiles), dim3(256), 0, (hipStream_t)stream, src, dst, (const long*)table);
-  GAD_LAUNCH_CHECK("gad_wino_weights");
-  return 0;
-}
-
-extern "C" int gad_wino4_weights(const float* src, float* dst, const int64_t* table, int64_t n_tiles, void* stream) {
-  GAD_CHECK(src && dst && table && n_tiles > 0 && n_tiles < (1L << 31), "gad_wino4_weights: bad arguments");
-  hipLaunchKernelGGL(wino4_weights_kernel, dim3((unsigned)n_tiles), dim3(256), 0, (hipStream_t)stream, src, dst, (const long*)table);
-  GAD_LAUNCH_CHECK("gad_wino4_weights");
-  return 0;
-}
-
 // ---- gad_gemm: check the arguments, resolve the route, dispatch on its kind ----
 
 // shape / alignment contracts of the float4 paths (checked on the host so that a mismatch is an error, never an
@@ -3108,123 +2329,6 @@ static DevArgs dev_args(const gad_gemm_args* a) {
                (!a->rowadd || (gad_aligned16(a->rowadd) && a->ld_rowadd % 4 == 0)) &&
                (!a->residual || (gad_aligned16(a->residual) && a->ldr % 4 == 0)) && (!a->ws || gad_aligned16(a->ws))) ? 1 : 0;
   return d;
-}
-
-static int launch_wino_wgrad(const Route& r, void* stream) {
-  const gad_gemm_args* a = &r.a;
-  const WinoWgradPlan& wq = r.wq;
-  const gad_conv_geom& g = a->g;
-  hipStream_t st = (hipStream_t)stream;
-  GAD_CHECK(a->wino_ws && a->wino_ws_bytes >= wq.bytes && gad_aligned16(a->wino_ws),
-            "gad_gemm: Winograd weight-gradient workspace too small or misaligned (%lld < %lld)", (long long)a->wino_ws_bytes, (long long)wq.bytes);
-  float* Wy = (float*)a->wino_ws;
-  float* V = Wy + wq.wy_bytes / 4;
-  float* dU = V + wq.v_bytes / 4;
-  // the forward launch of the same convolution already made B^T x B (its V, same geometry => same [36][T][Cin] image): a caller
-  // that kept it passes it as B_wino4 with GAD_GEMM_WINO_SKIP_INPUT and the input transform is not run again
-  const bool have_v = (a->flags & GAD_GEMM_WINO_SKIP_INPUT) && a->B_wino4 != nullptr;
-  if (have_v) {
-    GAD_CHECK(gad_aligned16(a->B_wino4), "gad_gemm: the kept Winograd input image (B_wino4 of a weight-gradient launch) must be 16-byte aligned");
-    V = const_cast<float*>(a->B_wino4);
-  }
-  WinoIn wy;                                     // dy [B][Ho][Wo][Cout] -> Wy
-  wy.x = a->A; wy.V = Wy;
-  wy.H = g.Ho; wy.W = g.Wo; wy.C = a->M; wy.ldx = a->lda; wy.up = 0;
-  wy.TH = g.Ho / 4; wy.TW = g.Wo / 4; wy.T = wq.T;
-  WinoIn wi;                                     // x -> V, as in the forward pass
-  wi.x = a->B; wi.V = V;
-  wi.H = g.H; wi.W = g.W; wi.C = g.C; wi.ldx = g.ldx; wi.up = g.upsample ? 1 : 0;
-  wi.TH = wy.TH; wi.TW = wy.TW; wi.T = wq.T;
-  const long iy = wq.T * (a->M / 4), ix = wq.T * (g.C / 4);
-  GAD_CHECK(gad_ceil_div(iy, 256) < (1L << 31) && gad_ceil_div(ix, 256) < (1L << 31), "gad_gemm: Winograd transform grid too large");
-  hipLaunchKernelGGL(wino4_dy_kernel, dim3((unsigned)gad_ceil_div(iy, 256)), dim3(256), 0, st, wy);
-  if (!have_v) hipLaunchKernelGGL(wino4_input_kernel, dim3((unsigned)gad_ceil_div(ix, 256)), dim3(256), 0, st, wi);
-  GAD_LAUNCH_CHECK("gad_gemm(winograd wgrad transforms)");
-  const gad_gemm_args sub = wino_wgrad_products_args(a, wq, Wy, V, dU);
-  if (const int rc = gad_gemm(&sub, stream)) return rc;
-  const long items = (long)a->M * (g.C / 4);
-  hipLaunchKernelGGL(wino4_dw_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, dU, a->C, a->M, g.C, a->ldc);
-  GAD_LAUNCH_CHECK("gad_gemm(winograd wgrad output transform)");
-  return 0;
-}
-
-static int launch_wino(const Route& r, const DevArgs& d, void* stream) {
-  const gad_gemm_args* a = &r.a;
-  const WinoPlan& wp = r.wp;
-  const gad_conv_geom& g = a->g;
-  hipStream_t st = (hipStream_t)stream;
-  GAD_CHECK(a->wino_ws && a->wino_ws_bytes >= wp.bytes && gad_aligned16(a->wino_ws) && gad_aligned16(wp.f == 2 ? a->B_wino : a->B_wino4),
-            "gad_gemm: Winograd workspace too small or misaligned (%lld < %lld)", (long long)a->wino_ws_bytes, (long long)wp.bytes);
-  WinoIn wi;
-  wi.x = a->A; wi.V = (float*)a->wino_ws;
-  wi.H = g.H; wi.W = g.W; wi.C = g.C; wi.ldx = g.ldx; wi.up = g.upsample ? 1 : 0;
-  wi.TH = g.Ho / wp.f; wi.TW = g.Wo / wp.f; wi.T = wp.T;
-  const long items = wp.T * (g.C / 4);
-  GAD_CHECK(gad_ceil_div(items, 256) < (1L << 31), "gad_gemm: Winograd input transform grid too large");
-  const bool only_input = (a->flags & GAD_GEMM_WINO_ONLY_INPUT) != 0, skip_input = (a->flags & GAD_GEMM_WINO_SKIP_INPUT) != 0;
-  auto products = [&](const float* U) {          // the product kernels of F(2x2) and of the one-launch F(4x4): V x U + output transform
-    DevArgs w = d;
-    w.A = wi.V; w.B = U;
-    w.M = (int)wp.T; w.N = a->N; w.K = g.C;
-    w.lda = g.C; w.ldb = g.C;
-    w.sA0 = wp.T * (long)g.C; w.sB0 = (long)a->N * g.C;
-    w.fdHoWo = make_fastdiv((unsigned)(wi.TH * wi.TW));
-    w.fdWo = make_fastdiv((unsigned)wi.TW);
-    w.tiles_m = wp.tiles_m; w.tiles_n = wp.tiles_n;
-    return w;
-  };
-  if (wp.f == 4) {
-    if (!skip_input) {
-      hipLaunchKernelGGL(wino4_input_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, wi);
-      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 input transform)");
-    }
-    if (only_input) return 0;
-    if (wp.fused4 == 2) {                        // products + the whole output transform in one launch
-      GAD_CHECK((long)wp.tiles_m * wp.tiles_n < (1L << 31), "gad_gemm: Winograd grid too large");
-      gadk::launch_wino4_fused(products(a->B_wino4), wp.bm, st);
-      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 fused products + output transform)");
-      return 0;
-    }
-    float* Mb = wi.V + 36 * wp.T * (long)g.C;
-    WinoOut wo;
-    wo.Mb = Mb; wo.y = a->C; wo.bias = a->bias; wo.rowadd = a->rowadd; wo.residual = a->residual;
-    wo.N = a->N; wo.ldc = a->ldc; wo.ldr = a->ldr; wo.ld_rowadd = a->ld_rowadd;
-    wo.Ho = g.Ho; wo.Wo = g.Wo; wo.TH = wi.TH; wo.TW = wi.TW; wo.T = wp.T; wo.alpha = a->alpha;
-    const long oitems = wp.T * (a->N / 4);
-    if (wp.fused4 == 1) {
-      DevArgs w = d;
-      w.A = wi.V; w.B = a->B_wino4; w.C = Mb;
-      w.M = (int)wp.T; w.N = a->N; w.K = g.C;
-      w.lda = g.C; w.ldb = g.C; w.ldc = a->N;
-      w.sA0 = wp.T * (long)g.C; w.sB0 = (long)a->N * g.C; w.sC0 = wp.T * (long)a->N;
-      w.tiles_m = wp.tiles_m; w.tiles_n = wp.tiles_n;
-      w.splitk = 1; w.bias = nullptr; w.rowadd = nullptr; w.residual = nullptr; w.alpha = 1.f;
-      w.epi_vec = 1;                             // Mh is 16-byte aligned scratch, N % 4 == 0
-      dim3 grid((unsigned)((long)wp.tiles_m * wp.tiles_n * 6)), block(NTHREADS);
-      if (wp.bm == 64) hipLaunchKernelGGL((wino4_gemm_kernel<64, 128>), grid, block, 0, st, w);
-      else hipLaunchKernelGGL((wino4_gemm_kernel<128, 64>), grid, block, 0, st, w);
-      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 products)");
-      hipLaunchKernelGGL(wino4_output_kernel<true>, dim3((unsigned)gad_ceil_div(oitems, 256)), dim3(256), 0, st, wo);
-      GAD_LAUNCH_CHECK("gad_gemm(winograd F4 output transform)");
-      return 0;
-    }
-    const gad_gemm_args sub = wino4_products_args(a, wp, wi.V, Mb);
-    if (const int rc = gad_gemm(&sub, stream)) return rc;
-    hipLaunchKernelGGL(wino4_output_kernel<false>, dim3((unsigned)gad_ceil_div(oitems, 256)), dim3(256), 0, st, wo);
-    GAD_LAUNCH_CHECK("gad_gemm(winograd F4 output transform)");
-    return 0;
-  }
-  if (!skip_input) {
-    hipLaunchKernelGGL(wino_input_kernel, dim3((unsigned)gad_ceil_div(items, 256)), dim3(256), 0, st, wi);
-    GAD_LAUNCH_CHECK("gad_gemm(winograd input transform)");
-  }
-  if (only_input) return 0;
-  const DevArgs w = products(a->B_wino);
-  dim3 grid((unsigned)((long)wp.tiles_m * wp.tiles_n)), block(NTHREADS);
-  if (wp.bm == 64) hipLaunchKernelGGL((wino_gemm_kernel<64, 128>), grid, block, 0, st, w);
-  else hipLaunchKernelGGL((wino_gemm_kernel<128, 64>), grid, block, 0, st, w);
-  GAD_LAUNCH_CHECK("gad_gemm(winograd)");
-  return 0;
 }
 
 static int launch_fewout(const Route& r, const DevArgs& d, hipStream_t st) {
@@ -3416,8 +2520,8 @@ extern "C" int gad_gemm(const gad_gemm_args* args, void* stream) {
       const int rc = gad_gemm(&lo, stream);
       return rc ? rc : gad_gemm(&hi, stream);
     }
-    case RouteKind::WINO_WGRAD: return launch_wino_wgrad(r, stream);
-    case RouteKind::WINO: return launch_wino(r, d, stream);
+    case RouteKind::WINO_WGRAD: return launch_wino_wgrad(&r.a, r.wq, stream);
+    case RouteKind::WINO: return launch_wino(&r.a, r.wp, d, stream);
     case RouteKind::FEWOUT: return launch_fewout(r, d, st);
     case RouteKind::WGRAD_PATCH: return launch_wgrad_patch(r, d, st);
     case RouteKind::PATCH_BF16: return launch_patch_bf16(r, d, st);

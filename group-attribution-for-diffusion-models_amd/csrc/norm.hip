@@ -10,7 +10,7 @@
 // Forward has a one-pass plan (gn_slab_kernel, below) that reads x once when an (image, channel slab) fits
 // in one workgroup's registers; the two-pass plan remains for the other shapes.
 #include "gad_reduce.h"
-#include "gemm_dev.h"
+#include "wino_dev.h"
 
 namespace {
 
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(512) void gn_wino4_kernel(const float* __restrict__
     }
   }
   __syncthreads();
-  // ---- 6 x 6 patches of one channel quad -> V (the arithmetic of wino4_input_kernel, gemm_f32.hip) ----
+  // ---- 6 x 6 patches of one channel quad -> V (the arithmetic of wino4_input_kernel, winograd.hip) ----
   const int H = s.HW / w.W;
   const int items = w.TH * w.TW * s.qpr;
   for (int it = tid; it < items; it += NTH) {

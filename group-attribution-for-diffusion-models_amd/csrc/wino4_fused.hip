@@ -1,6 +1,6 @@
 // Winograd F(4x4, 3x3) products with the WHOLE output transform kept on chip (gfx950).
 //
-// The three-launch route of gemm_f32.hip (wino4_input_kernel -> wino4_gemm_kernel -> wino4_output_kernel) sends the
+// The three-launch route of winograd.hip (wino4_input_kernel -> wino4_gemm_kernel -> wino4_output_kernel) sends the
 // half-transformed products Mh [24][tiles][Cout] out to HBM and back: 3 of the 9.5 tensor-sized streams of a convolution.
 // Here one workgroup owns a (64 tiles x 64 output channels) block for ALL 36 Winograd positions and never writes a product:
 //
@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "gemm_dev.h"
+#include "wino_dev.h"
 
 using namespace gadk;
 
@@ -70,6 +71,7 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
   }
 
   // ---- the prefetch stream: stage-step (pp, pk) is the next one to issue; past the end it re-reads the last one ----
+  // (spelled in both kernels: as one struct shared by them hipcc generated different code for every instance of both)
   int pp = 0, pk = 0;
   const long wrapA = p.sA0 - (long)kcs * (BK * SUB), wrapB = p.sB0 - (long)kcs * (BK * SUB);
   auto advance = [&]() {                         // branch-free (scalar selects): a K step stays one basic block for the scheduler
@@ -97,14 +99,8 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
   // One stage-step: 16 SUB MFMAs on stage cs into `cur`; the DMA of stage-step s + D goes into the stage multiplied one step
   // ago; FIRST (a position's first step): the finished product `oth` of position (., NUP) is folded into Y and cleared,
   // one accumulator register per MFMA gap.
-  float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;  // A^T column of the position being folded
-  auto set_nu = [&](int nu) {                    // [1 0 0 0], [1 1 1 1], [1 -1 1 -1], [1 2 4 8], [1 -2 4 -8], [0 0 0 1]
-    const float sg = (nu == 2 || nu == 4) ? -1.f : 1.f, two = nu >= 3 ? 2.f : 1.f;
-    w0 = nu == 5 ? 0.f : 1.f;
-    w1 = (nu == 0 || nu == 5) ? 0.f : sg * two;
-    w2 = (nu == 0 || nu == 5) ? 0.f : two * two;
-    w3 = nu == 0 ? 0.f : (nu == 5 ? 1.f : sg * two * two * two);
-  };
+  float w[4] = {0.f, 0.f, 0.f, 0.f};             // A^T column of the position being folded
+  auto set_nu = [&](int nu) { wino4_at_col(nu, w); };
   auto step = [&](auto first_c, f32x16& cur, f32x16& oth) {
     constexpr bool FIRST = decltype(first_c)::value != 0;
     const float* st = lds + cs * STAGE;
@@ -129,10 +125,10 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
           if (FIRST && sub == 0) {
             const int e = g * 4 + q4;
             const float a = oth[e];
-            Y[0][e] = __builtin_fmaf(w0, a, Y[0][e]);
-            Y[1][e] = __builtin_fmaf(w1, a, Y[1][e]);
-            Y[2][e] = __builtin_fmaf(w2, a, Y[2][e]);
-            Y[3][e] = __builtin_fmaf(w3, a, Y[3][e]);
+            Y[0][e] = __builtin_fmaf(w[0], a, Y[0][e]);
+            Y[1][e] = __builtin_fmaf(w[1], a, Y[1][e]);
+            Y[2][e] = __builtin_fmaf(w[2], a, Y[2][e]);
+            Y[3][e] = __builtin_fmaf(w[3], a, Y[3][e]);
             oth[e] = 0.f;
           }
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -147,20 +143,17 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
   };
   // xi direction: O[i][j] += A^T[i][xi] Y[j], Y = 0
   auto fold_xi = [&](int xi) {
-    const float sg = (xi == 2 || xi == 4) ? -1.f : 1.f, two = xi >= 3 ? 2.f : 1.f;
-    const float a0 = xi == 5 ? 0.f : 1.f;
-    const float a1 = (xi == 0 || xi == 5) ? 0.f : sg * two;
-    const float a2 = (xi == 0 || xi == 5) ? 0.f : two * two;
-    const float a3 = xi == 0 ? 0.f : (xi == 5 ? 1.f : sg * two * two * two);
+    float a[4];
+    wino4_at_col(xi, a);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float y = Y[j][e];
-        O[0][j][e] = __builtin_fmaf(a0, y, O[0][j][e]);
-        O[1][j][e] = __builtin_fmaf(a1, y, O[1][j][e]);
-        O[2][j][e] = __builtin_fmaf(a2, y, O[2][j][e]);
-        O[3][j][e] = __builtin_fmaf(a3, y, O[3][j][e]);
+        O[0][j][e] = __builtin_fmaf(a[0], y, O[0][j][e]);
+        O[1][j][e] = __builtin_fmaf(a[1], y, O[1][j][e]);
+        O[2][j][e] = __builtin_fmaf(a[2], y, O[2][j][e]);
+        O[3][j][e] = __builtin_fmaf(a[3], y, O[3][j][e]);
         Y[j][e] = 0.f;
       }
   };
@@ -180,10 +173,10 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const float a = accB[e];
-    Y[0][e] = __builtin_fmaf(w0, a, Y[0][e]);
-    Y[1][e] = __builtin_fmaf(w1, a, Y[1][e]);
-    Y[2][e] = __builtin_fmaf(w2, a, Y[2][e]);
-    Y[3][e] = __builtin_fmaf(w3, a, Y[3][e]);
+    Y[0][e] = __builtin_fmaf(w[0], a, Y[0][e]);
+    Y[1][e] = __builtin_fmaf(w[1], a, Y[1][e]);
+    Y[2][e] = __builtin_fmaf(w[2], a, Y[2][e]);
+    Y[3][e] = __builtin_fmaf(w[3], a, Y[3][e]);
   }
   fold_xi(5);
   wait_vm<0>();                                   // the re-read stage-steps past the end: nothing may land in the scratch below
@@ -194,7 +187,6 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
   const int rr = lane >> 3, c4 = (lane & 7) * 4;
   const int n = col0 + wn * 32 + c4;
   const bool n_ok = n < p.N;
-  const int tiles_img = (p.g.Ho >> 2) * (p.g.Wo >> 2), TW = p.g.Wo >> 2;
   long pix0[4];
   int img[4];
   bool m_ok[4];
@@ -203,10 +195,7 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
     const int m = row0 + wm * 32 + rr + 8 * q;
     m_ok[q] = m < p.M && n_ok;
     const int mm = m < p.M ? m : p.M - 1;
-    img[q] = p.fdHoWo.div(mm);
-    const int rem = mm - img[q] * tiles_img;
-    const int ty = p.fdWo.div(rem), tx = rem - ty * TW;
-    pix0[q] = ((long)img[q] * p.g.Ho + 4 * ty) * p.g.Wo + 4 * tx;
+    pix0[q] = tile_pixel0<4>(p, mm, img[q]);
   }
   f32x4 bias = zero4();
   if (p.bias && n_ok) bias = ldg4(p.bias + n);
@@ -249,27 +238,6 @@ __global__ __launch_bounds__(NTHREADS) void wino4_fused_kernel(const DevArgs p) 
 constexpr int EPI2_LD = 36;                      // scratch row stride (floats): rows e and e + 4 of a ds_write_b32 half land 16 banks apart
 constexpr int EPI2_WAVE = 16 * EPI2_LD;
 
-// k-contiguous operand rows by LDS-DMA for a workgroup of NTH threads (WinoKC's layout: slot i of a thread = row (tid >> 3) + (NTH / 8) i,
-// 16-byte chunk (tid & 7) swizzled by the row; rows beyond the operand clamp to the last one)
-template <int ROWS, int NTH>
-struct RowsKC {
-  static constexpr int RPS = NTH / 8, NS = ROWS / RPS;
-  static_assert(ROWS % RPS == 0, "whole slots");
-  const float* ptr[NS];
-  long off;
-  __device__ void init(const float* b, int ld, int row0, int nrows) {
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-      int r = row0 + (int)(threadIdx.x >> 3) + RPS * i;
-      r = r < nrows ? r : nrows - 1;
-      ptr[i] = b + (long)r * ld + ((threadIdx.x & 7) ^ ((threadIdx.x >> 4) & 7)) * 4;
-    }
-    off = 0;
-  }
-  __device__ __forceinline__ const float* src(int i) const { return ptr[i] + off; }
-  __device__ static float* dma_dst(float* tile, int i) { return tile + (wave_id() * 8 + RPS * i) * BK; }
-};
-
 // WM x WN waves of 16 tiles x 32 channels: 2 x 2 (32 tiles x 64 channels) or 4 x 1 (64 tiles x 32 channels: output widths that are
 // multiples of 32 but not of 64 - the pruned models' 96 / 160 / 224 / 288 - without a quarter of the MFMA work on padding);
 // 256 threads and two workgroups per CU either way.  (4 x 2 - 512 threads, one U tile for eight waves - measured no faster.)
@@ -277,8 +245,8 @@ template <int WM, int WN, int SUB, int NST>
 __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const DevArgs p) {
   constexpr int NTH = 64 * WM * WN, BM = 16 * WM, BN = 32 * WN, D = NST - 1;
   constexpr int A_TILE = BK * BM, SUBT = BK * (BM + BN), STAGE = SUB * SUBT;
-  using AL = RowsKC<BM, NTH>;
-  using BL = RowsKC<BN, NTH>;
+  using AL = WinoKC<BM, NTH>;
+  using BL = WinoKC<BN, NTH>;
   constexpr int NDA = AL::NS, NDB = BL::NS, NDS = NDA + NDB, NDMA = NDS * SUB;      // LDS-DMA wave-instructions per thread: per 32-deep sub-tile, per stage-step
   static_assert(NST * STAGE >= WM * WN * EPI2_WAVE, "the epilogue scratch lives in the ring");
   __shared__ __attribute__((aligned(16))) float lds[NST * STAGE];
@@ -338,14 +306,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
   barrier_vm<NDMA * (D - 1)>();
 
   int cs = 0;
-  float w0 = 0.f, w1 = 0.f, w2 = 0.f, w3 = 0.f;
-  auto set_nu = [&](int nu) {
-    const float sg = (nu == 2 || nu == 4) ? -1.f : 1.f, two = nu >= 3 ? 2.f : 1.f;
-    w0 = nu == 5 ? 0.f : 1.f;
-    w1 = (nu == 0 || nu == 5) ? 0.f : sg * two;
-    w2 = (nu == 0 || nu == 5) ? 0.f : two * two;
-    w3 = nu == 0 ? 0.f : (nu == 5 ? 1.f : sg * two * two * two);
-  };
+  float w[4] = {0.f, 0.f, 0.f, 0.f};
+  auto set_nu = [&](int nu) { wino4_at_col(nu, w); };
   auto step = [&](auto first_c, f32x4 (&cur)[2], f32x4 (&oth)[2]) {
     constexpr bool FIRST = decltype(first_c)::value != 0;
     const float* st = lds + cs * STAGE;
@@ -375,10 +337,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
           if (FIRST && pc < 8) {                              // fold register pc of the finished position
             const int c = pc >> 2, e = pc & 3;
             const float a = oth[c][e];
-            Y[0][c][e] = __builtin_fmaf(w0, a, Y[0][c][e]);
-            Y[1][c][e] = __builtin_fmaf(w1, a, Y[1][c][e]);
-            Y[2][c][e] = __builtin_fmaf(w2, a, Y[2][c][e]);
-            Y[3][c][e] = __builtin_fmaf(w3, a, Y[3][c][e]);
+            Y[0][c][e] = __builtin_fmaf(w[0], a, Y[0][c][e]);
+            Y[1][c][e] = __builtin_fmaf(w[1], a, Y[1][c][e]);
+            Y[2][c][e] = __builtin_fmaf(w[2], a, Y[2][c][e]);
+            Y[3][c][e] = __builtin_fmaf(w[3], a, Y[3][c][e]);
             oth[c][e] = 0.f;
           }
           __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
@@ -392,11 +354,8 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
     barrier_vm<NDMA * (D - 1)>();
   };
   auto fold_xi = [&](int xi) {
-    const float sg = (xi == 2 || xi == 4) ? -1.f : 1.f, two = xi >= 3 ? 2.f : 1.f;
-    const float a0 = xi == 5 ? 0.f : 1.f;
-    const float a1 = (xi == 0 || xi == 5) ? 0.f : sg * two;
-    const float a2 = (xi == 0 || xi == 5) ? 0.f : two * two;
-    const float a3 = xi == 0 ? 0.f : (xi == 5 ? 1.f : sg * two * two * two);
+    float a[4];
+    wino4_at_col(xi, a);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -404,10 +363,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float y = Y[j][c][e];
-          O[0][j][c][e] = __builtin_fmaf(a0, y, O[0][j][c][e]);
-          O[1][j][c][e] = __builtin_fmaf(a1, y, O[1][j][c][e]);
-          O[2][j][c][e] = __builtin_fmaf(a2, y, O[2][j][c][e]);
-          O[3][j][c][e] = __builtin_fmaf(a3, y, O[3][j][c][e]);
+          O[0][j][c][e] = __builtin_fmaf(a[0], y, O[0][j][c][e]);
+          O[1][j][c][e] = __builtin_fmaf(a[1], y, O[1][j][c][e]);
+          O[2][j][c][e] = __builtin_fmaf(a[2], y, O[2][j][c][e]);
+          O[3][j][c][e] = __builtin_fmaf(a[3], y, O[3][j][c][e]);
           Y[j][c][e] = 0.f;
         }
   };
@@ -429,10 +388,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float a = accB[c][e];
-      Y[0][c][e] = __builtin_fmaf(w0, a, Y[0][c][e]);
-      Y[1][c][e] = __builtin_fmaf(w1, a, Y[1][c][e]);
-      Y[2][c][e] = __builtin_fmaf(w2, a, Y[2][c][e]);
-      Y[3][c][e] = __builtin_fmaf(w3, a, Y[3][c][e]);
+      Y[0][c][e] = __builtin_fmaf(w[0], a, Y[0][c][e]);
+      Y[1][c][e] = __builtin_fmaf(w[1], a, Y[1][c][e]);
+      Y[2][c][e] = __builtin_fmaf(w[2], a, Y[2][c][e]);
+      Y[3][c][e] = __builtin_fmaf(w[3], a, Y[3][c][e]);
     }
   fold_xi(5);
   wait_vm<0>();
@@ -443,7 +402,6 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
   const int rr = lane >> 3, c4 = (lane & 7) * 4;
   const int n = col0 + wn * 32 + c4;
   const bool n_ok = n < p.N;
-  const int tiles_img = (p.g.Ho >> 2) * (p.g.Wo >> 2), TW = p.g.Wo >> 2;
   long pix0[2];
   int img[2];
   bool m_ok[2];
@@ -452,10 +410,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino4_fused2_kernel(const Dev
     const int m = row0 + wm * 16 + rr + 8 * q;
     m_ok[q] = m < p.M && n_ok;
     const int mm = m < p.M ? m : p.M - 1;
-    img[q] = p.fdHoWo.div(mm);
-    const int rem = mm - img[q] * tiles_img;
-    const int ty = p.fdWo.div(rem), tx = rem - ty * TW;
-    pix0[q] = ((long)img[q] * p.g.Ho + 4 * ty) * p.g.Wo + 4 * tx;
+    pix0[q] = tile_pixel0<4>(p, mm, img[q]);
   }
   f32x4 bias = zero4();
   if (p.bias && n_ok) bias = ldg4(p.bias + n);

@@ -397,8 +397,16 @@ def wino4_wgrad(x, dy, ups=False):
 
 
 # ------------------------------------------------------------------------------------------ conditioning cases ----
-COND_SHAPES = {"64": (2, 64, 64, 16, 16), "68": (2, 64, 68, 16, 16)}       # B, Cin, Cout, H, W; 68: the ragged channel block
+# B, Cin, Cout, H, W; 68: the ragged channel block; 32: Cin is no multiple of 64, so the one-launch F(4x4) forms run their 32-deep
+# stage-steps on the four-stage ring (the other ring depth and wait count)
+COND_SHAPES = {"64": (2, 64, 64, 16, 16), "68": (2, 64, 68, 16, 16), "32": (2, 32, 64, 16, 16)}
 SIX_POSITION_SHAPE = (171, 32, 128, 32, 32)     # the cheapest launch with tiles_m * tiles_n * 6 >= 1024: 64 x 128 blocks, T / 64 = B = 171, one 32-channel chunk
+# The other block shape of the six-position kernel.  use_wino pads Cout to the block's channels: Cout = 64 pads to 64 on 64-channel
+# blocks and to 128 on 128-channel ones, so it takes (128 tiles x 64 channels); T = 342 * 64 = 21888 tiles -> 171 x 1 blocks, x 6
+# = 1026 >= 1024, the threshold of the six-position form.  (The plan query reports tile 128 for both block shapes; the 24-panel
+# scratch size tells the six-position form from the 36 batched products.)
+SIX_POSITION_SHAPE_128x64 = (342, 32, 64, 32, 32)
+SIX_POSITION_SHAPES = {"six": SIX_POSITION_SHAPE, "six-128x64": SIX_POSITION_SHAPE_128x64}
 SPIKES = ((0, 0), (7, 9))                       # a corner pixel and an interior one (no 6 x 6 window holds both)
 COND_NAMES = ("randn", "silu", "offset(30,1)", "hot_channel", "spike", "highpass_ramp", "constant")
 

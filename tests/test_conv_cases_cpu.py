@@ -78,6 +78,12 @@ def test_every_kernel_family_has_a_case(lib):
     small = CC.plan_args(CC._r("six-1", B - 1, Ci, Co, H, W, 3, 3, 1, CC.P1), "fwd", hint=10, no_wino4=False)          # 170 x 1 x 6 < 1024 blocks
     T = (B - 1) * H * W // 16
     assert lib.gad_gemm_wino_bytes(ctypes.byref(small)) == 4 * (36 * T * Ci + 36 * T * Co)
+    # ... and on its (128 tiles x 64 channels) blocks: 171 x 1 x 6 = 1026 blocks
+    B, Ci, Co, H, W = CC.SIX_POSITION_SHAPE_128x64
+    big = CC.plan_args(CC._r("six-128x64", B, Ci, Co, H, W, 3, 3, 1, CC.P1), "fwd", hint=10, no_wino4=False)
+    T = B * H * W // 16
+    assert -(-T // 128) * -(-Co // 64) * 6 == 1026
+    assert CC.plan(big)[0] == 6 and lib.gad_gemm_wino_bytes(ctypes.byref(big)) == 4 * (36 * T * Ci + 24 * T * Co)
 
 
 def test_the_edge_table_is_whole():

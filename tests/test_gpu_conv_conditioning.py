@@ -44,7 +44,7 @@ def reference(name, shape_key, algorithm):
     """computed once, shared, left unchanged"""
     key = (name, shape_key, algorithm)
     if key not in _REF:
-        shape = CC.COND_SHAPES.get(shape_key, CC.SIX_POSITION_SHAPE)
+        shape = CC.COND_SHAPES.get(shape_key) or CC.SIX_POSITION_SHAPES[shape_key]
         _REF[key] = CC.cond_forward_reference(*CC.cond_inputs(name, shape), algorithm)
     return _REF[key]
 
@@ -86,20 +86,31 @@ def test_every_route_is_inside_the_bound(ops, name, shape_key):
     assert not bad, "outside K * max(e_ref, 2^-22 max|want|):\n" + "\n".join(bad)
 
 
-@pytest.mark.parametrize("name", ["randn", "spike"])
-def test_six_position_product_kernel_is_inside_the_bound(ops, name):
-    """the three-launch F(4x4) form at >= 1024 product blocks: 24 half-transformed panels instead of 36 products"""
-    shape = CC.SIX_POSITION_SHAPE
+def six_position(ops, name, shape_key):
+    shape = CC.SIX_POSITION_SHAPES[shape_key]
     x, w = CC.cond_inputs(name, shape)
     T = shape[0] * shape[3] * shape[4] // 16
     from gad import _capi
     import ctypes
-    a = CC.plan_args(CC._r("six", *shape, 3, 3, 1, CC.P1), "fwd", hint=10, no_wino4=False)
+    a = CC.plan_args(CC._r(shape_key, *shape, 3, 3, 1, CC.P1), "fwd", hint=10, no_wino4=False)
+    assert _capi.load().gad_gemm_kernel_id(ctypes.byref(a)) == 6
     assert _capi.load().gad_gemm_wino_bytes(ctypes.byref(a)) == 4 * (36 * T * shape[1] + 24 * T * shape[2])
-    want, e_ref = reference(name, "six", "wino4")
+    want, e_ref = reference(name, shape_key, "wino4")
     err, b, line = CC.figure(run(ops, x, w, "wino4-three-launch"), want, e_ref, f"COND fwd wino4-six-position {name} {shape}")
     print(line, flush=True)
     assert err <= b, line
+
+
+@pytest.mark.parametrize("name", ["randn", "spike"])
+def test_six_position_product_kernel_is_inside_the_bound(ops, name):
+    """the three-launch F(4x4) form at >= 1024 product blocks: 24 half-transformed panels instead of 36 products"""
+    six_position(ops, name, "six")
+
+
+@pytest.mark.parametrize("name", ["randn", "spike"])
+def test_six_position_product_kernel_on_128x64_blocks_is_inside_the_bound(ops, name):
+    """the same on (128 tiles x 64 channels) blocks: Cout = 64 (conv_cases.SIX_POSITION_SHAPE_128x64 derives the plan)"""
+    six_position(ops, name, "six-128x64")
 
 
 def _window_mask(H, W, f):

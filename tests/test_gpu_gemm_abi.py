@@ -1,4 +1,4 @@
-"""gad_gemm's generic engine (csrc/gemm_f32.hip: gemm_kernel, gemm_bf16_kernel, splitk_reduce_kernel, store_block) on padded,
+"""gad_gemm's generic engine (csrc/gemm_f32.hip: gemm_kernel, gemm_bf16_kernel, splitk_reduce_kernel; csrc/gemm_dev.h: store_block) on padded,
 batched and misaligned operands, EXACTLY: integer operands whose every partial sum fp32 (and bf16 rounding) represents, the
 whole output buffer - row padding, gaps between batch slabs, floats before an offset pointer - compared with torch.equal
 against the CPU restatement of the ABI (tests/gemm_ref.py; cases: tests/gemm_cases.py, checked on the CPU by

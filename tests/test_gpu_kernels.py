@@ -1155,7 +1155,7 @@ def test_attention_fused_qkv_inference_path_is_bit_identical(ops, monkeypatch):
 
 @pytest.mark.parametrize("prec", ["f32", "bf16"])
 def test_float4_epilogue_is_bit_identical_to_scalar_stores(ops, prec):
-    """The LDS-transposed float4 epilogue (csrc/gemm_f32.hip::store_block) against dword stores straight from the
+    """The LDS-transposed float4 epilogue (csrc/gemm_dev.h::store_block) against dword stores straight from the
     accumulators (kernel_flags(scalar_epilogue=True)): same arithmetic per element, so the outputs must be equal bit
     for bit - with bias, alpha, time-embedding row add and residual fused, ragged M (last tile partly outside), N that
     is a multiple of 4 but not of the tile, split-K partials, batched outputs, 64- and 128-wide tiles, the 3x3 patch
