@@ -88,6 +88,20 @@ class AdamArgs(C.Structure):
                 ("weight_decay", C.c_float), ("adamw", C.c_int32), ("step", C.c_int32), ("ema_decay", C.c_float)]
 
 
+class Adam8Block(C.Structure):
+    """gad_adam8_block (include/gad.h): one run of at most 2048 elements of one parameter"""
+    _fields_ = [("offset", C.c_int64), ("len", C.c_int32), ("state", C.c_int32), ("weight_decay", C.c_float), ("fp32", C.c_int32)]
+
+
+class Adam8Args(C.Structure):
+    """gad_adam8_args (include/gad.h): fused clip + 8-bit blockwise Adam + EMA"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("ema", C.c_void_p), ("state1", C.c_void_p), ("state2", C.c_void_p),
+                ("absmax1", C.c_void_p), ("absmax2", C.c_void_p), ("m32", C.c_void_p), ("v32", C.c_void_p), ("blocks", C.c_void_p),
+                ("n", C.c_int64), ("n32", C.c_int64), ("n_absmax", C.c_int32), ("n_blocks", C.c_int32),
+                ("sumsq", C.c_void_p), ("max_norm", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("eps", C.c_float), ("step", C.c_int32), ("ema_decay", C.c_float)]
+
+
 class JLArgs(C.Structure):
     """gad_jl_args (include/gad.h): random projection of gradient rows (TRAK / D-TRAK features)"""
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int64), ("G", C.c_int32), ("P", C.c_int64), ("p0", C.c_int64),
@@ -178,6 +192,8 @@ SIGNATURES = {
     "gad_sumsq": (C.c_int, [_vp, _vp, _i64, _vp, _i64, _vp]),
     "gad_clip_adam_ema": (C.c_int, [C.POINTER(AdamArgs), _vp]),
     "gad_ema_update": (C.c_int, [_vp, _vp, _i64, _f32, _vp]),
+    "gad_adam8_qmap": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
+    "gad_clip_adam8_ema": (C.c_int, [C.POINTER(Adam8Args), _vp]),
     # half-precision activation path (csrc/half.hip, csrc/attention.hip)
     "gad_hgemm_workspace_bytes": (_i64, [C.POINTER(HGemmArgs)]),
     "gad_hgemm_plan": (C.c_int, [C.POINTER(HGemmArgs), C.POINTER(_i32), C.POINTER(_i32)]),

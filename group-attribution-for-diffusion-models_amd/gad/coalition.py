@@ -195,7 +195,7 @@ class CoalitionEngine:
     def __init__(self, dataset_name="cifar100", device="cuda:0", base_state: Optional[dict] = None,
                  gd_steps: Optional[int] = None, n_samples=10240, sample_batch=32, fuse=32,
                  num_inference_steps=100, opt_seed=42, by_class=True, preview=True,
-                 unet_overrides: Optional[dict] = None, feature_dims=2048):
+                 unet_overrides: Optional[dict] = None, feature_dims=2048, optim_bits=32):
         from src.datasets import create_dataset
         from src.ddpm_config import DDPMConfig
         from .scoring import extractor_tag  # noqa: F401
@@ -231,6 +231,7 @@ class CoalitionEngine:
         scoring._REF_STATS[scoring.net_key("fid")] = self.feature_net          # one extractor for every score of this process
         self.opt_kwargs = dict(self.config["optimizer_config"]["kwargs"])
         self.adamw = self.config["optimizer_config"]["class_name"] == "AdamW"
+        self.optim_bits = optim_bits          # 8: the trainers keep blockwise 8-bit Adam state (--use_8bit_optimizer)
 
     # -- pieces ---------------------------------------------------------------------------------
     def coalition(self, removal_seed: int):
@@ -247,6 +248,9 @@ class CoalitionEngine:
 
     def make_trainer(self, model, ema):
         kw = self.opt_kwargs
+        if self.optim_bits == 8:     # unlearn.py:446-477: Adam8bit, the config's decay on every parameter whose name lacks "bias"
+            return FusedTrainer(model, self.train_scheduler, ema, lr=kw.get("lr", 1e-4), weight_decay=kw["weight_decay"],
+                                max_grad_norm=1.0, optim_bits=8, no_decay=["bias" in n for n, _ in model.named_parameters()])
         return FusedTrainer(model, self.train_scheduler, ema, lr=kw.get("lr", 1e-4),
                             weight_decay=kw.get("weight_decay", 0.0), adamw=self.adamw, max_grad_norm=1.0)
 

@@ -15,7 +15,7 @@ from typing import Optional
 import torch
 
 from . import _capi
-from ._capi import (A_CONV, A_CONVT, A_KC, A_MC, B_CONV, B_KC, B_MC, B_WDGRAD, AdamArgs, ConvGeom, GemmArgs,
+from ._capi import (A_CONV, A_CONVT, A_KC, A_MC, B_CONV, B_KC, B_MC, B_WDGRAD, Adam8Args, AdamArgs, ConvGeom, GemmArgs,
                     GroupNormArgs, check)
 from .shadows import (WEIGHT_EPOCH, Shadow, cached, in_flat_buffer as _in_flat_buffer, weight_key, written,  # noqa: F401
                       written_everywhere)
@@ -1749,6 +1749,35 @@ def clip_adam_ema_raw(p, g, m, v, ema, sumsq, *, max_norm, lr, betas, eps, weigh
     a.lr, a.beta1, a.beta2, a.eps, a.weight_decay = lr, betas[0], betas[1], eps, weight_decay
     a.adamw, a.step, a.ema_decay = int(adamw), step, ema_decay
     check(_capi.load().gad_clip_adam_ema(C.byref(a), _stream()), "gad_clip_adam_ema")
+
+
+def adam8_qmap(signed: bool) -> torch.Tensor:
+    """The 256 ascending fp32 code values of the 8-bit optimizer's signed / unsigned map (host tensor; needs no GPU)"""
+    buf = (C.c_float * 256)()
+    check(_capi.load().gad_adam8_qmap(int(bool(signed)), buf), "gad_adam8_qmap")
+    return torch.tensor(list(buf), dtype=torch.float32)
+
+
+def clip_adam8_ema_raw(p, g, ema, state1, state2, absmax1, absmax2, m32, v32, blocks, sumsq, *, max_norm, lr, betas, eps, step, ema_decay):
+    """Fused clip + 8-bit blockwise Adam + EMA (gad_clip_adam8_ema).  `blocks`: uint8 device tensor holding the gad_adam8_block
+    table (training.adam8_blocks); each block carries its own decoupled weight decay."""
+    written(p)        # as clip_adam_ema_raw: the raw kernel moves the flat buffer's residents
+    if state1.dtype != torch.uint8 or state2.dtype != torch.uint8 or state1.numel() != p.numel() or state2.numel() != p.numel():
+        raise _capi.GadError("clip_adam8_ema: state1 / state2 must be uint8 buffers as long as the flat parameter buffer")
+    if absmax1.numel() != absmax2.numel() or m32.numel() != v32.numel() or g.numel() != p.numel():
+        raise _capi.GadError("clip_adam8_ema: buffer lengths do not match")
+    if blocks.dtype != torch.uint8 or blocks.numel() % C.sizeof(_capi.Adam8Block) or not blocks.is_contiguous():
+        raise _capi.GadError("clip_adam8_ema: blocks is not a contiguous uint8 image of a gad_adam8_block table")
+    a = Adam8Args()
+    a.p, a.g, a.ema = p.data_ptr(), g.data_ptr(), _ptr(ema)
+    a.state1, a.state2, a.absmax1, a.absmax2 = state1.data_ptr(), state2.data_ptr(), absmax1.data_ptr(), absmax2.data_ptr()
+    a.m32, a.v32, a.blocks = m32.data_ptr(), v32.data_ptr(), blocks.data_ptr()
+    a.n, a.n32, a.n_absmax, a.n_blocks = p.numel(), m32.numel(), absmax1.numel(), blocks.numel() // C.sizeof(_capi.Adam8Block)
+    a.sumsq = _ptr(sumsq)
+    a.max_norm = max_norm
+    a.lr, a.beta1, a.beta2, a.eps = lr, betas[0], betas[1], eps
+    a.step, a.ema_decay = step, ema_decay
+    check(_capi.load().gad_clip_adam8_ema(C.byref(a), _stream()), "gad_clip_adam8_ema")
 
 
 def ema_update_raw(ema, p, decay: float):

@@ -100,6 +100,121 @@ def adam_state_from_torch(sd, params, m, v):
     return step
 
 
+ADAM8_BLOCK, ADAM8_MIN_SIZE = 2048, 4096      # bitsandbytes' blockwise block size and min_8bit_size
+
+
+class Adam8Layout:
+    """What `adam8_blocks` returns.  `table`: numpy structured array with the fields of gad_adam8_block (include/gad.h), one row
+    per block, in flat-buffer order.  `params`: per parameter (fp32 flag, flat offset, numel, first absmax index or side-moment
+    offset, number of blocks).  `n_absmax`: 8-bit blocks in all.  `n32`: floats of fp32 side moments (slot-packed like the flat
+    buffer, small parameters only)."""
+
+    def __init__(self, table, params, n_absmax, n32):
+        self.table, self.params, self.n_absmax, self.n32 = table, params, n_absmax, n32
+
+
+def adam8_blocks(params, weight_decay, no_decay=()):
+    """Block descriptors of the 8-bit optimizer over the flat buffer `flatten_params(params)` lays out (pure host code).
+    A parameter of at least ADAM8_MIN_SIZE elements is cut into runs of ADAM8_BLOCK elements of its STORAGE order (conv weights:
+    [Cout, KH, KW, Cin]), the last one as short as it comes out; a smaller one keeps fp32 moments and is cut the same way only to
+    share the launch.  No block crosses a parameter or covers the padding that brings a parameter to a whole SLOT.
+    `no_decay`: per-parameter mask; a masked parameter's blocks carry weight decay 0."""
+    import numpy as np
+    params = list(params)
+    no_decay = list(no_decay) if len(no_decay) else [False] * len(params)
+    if len(no_decay) != len(params):
+        raise ValueError(f"adam8_blocks: no_decay masks {len(no_decay)} parameters, there are {len(params)}")
+    dt = np.dtype([("offset", "<i8"), ("len", "<i4"), ("state", "<i4"), ("weight_decay", "<f4"), ("fp32", "<i4")])
+    rows, info = [], []
+    off = n_absmax = n32 = 0
+    for p, skip in zip(params, no_decay):
+        n = int(p.numel())
+        small = n < ADAM8_MIN_SIZE
+        wd = 0.0 if skip else float(weight_decay)
+        first = n32 if small else n_absmax
+        nb = 0
+        for s in range(0, n, ADAM8_BLOCK):
+            ln = min(ADAM8_BLOCK, n - s)
+            rows.append((off + s, ln, n32 + s if small else n_absmax, wd, int(small)))
+            nb += 1
+            if not small:
+                n_absmax += 1
+        if small:
+            n32 += _slot(n)
+        info.append((small, off, n, first, nb))
+        off += _slot(n)
+    return Adam8Layout(np.array(rows, dtype=dt), info, n_absmax, n32)
+
+
+def _storage_view(buf, off, p):
+    """Logical-shape view of the n = p.numel() elements of `buf` at `off`, laid out in p's storage order"""
+    n = p.numel()
+    if p.ndim == 4:
+        o, i, kh, kw = p.shape
+        return buf[off:off + n].view(o, kh, kw, i).permute(0, 3, 1, 2)
+    return buf[off:off + n].view(p.shape)
+
+
+def adam8_state_to_dict(params, layout, bufs, step, hp):
+    """8-bit optimizer state under bitsandbytes' key names, per parameter: `state1` / `state2` (uint8 codes in the parameter's
+    shape, or fp32 moments for a parameter below ADAM8_MIN_SIZE), `absmax1` / `absmax2` (one per block), `qmap1` / `qmap2`, `step`.
+    The blocks run over this engine's storage order, so the absmax values belong to these codes and not to bitsandbytes' own."""
+    state = {}
+    if step > 0:
+        qmap1, qmap2 = ops.adam8_qmap(True), ops.adam8_qmap(False)
+        for i, (p, (small, off, n, first, nb)) in enumerate(zip(params, layout.params)):
+            if small:
+                state[i] = {"step": step, "state1": _storage_view(bufs["m32"], first, p).detach().cpu().contiguous(),
+                            "state2": _storage_view(bufs["v32"], first, p).detach().cpu().contiguous()}
+            else:
+                state[i] = {"step": step, "state1": _storage_view(bufs["state1"], off, p).detach().cpu().contiguous(),
+                            "state2": _storage_view(bufs["state2"], off, p).detach().cpu().contiguous(),
+                            "absmax1": bufs["absmax1"][first:first + nb].detach().cpu().clone(),
+                            "absmax2": bufs["absmax2"][first:first + nb].detach().cpu().clone(),
+                            "qmap1": qmap1, "qmap2": qmap2}
+    group = {"lr": hp["lr"], "betas": tuple(hp["betas"]), "eps": hp["eps"], "weight_decay": hp["weight_decay"], "optim_bits": 8,
+             "block_wise": True, "min_8bit_size": ADAM8_MIN_SIZE, "percentile_clipping": 100, "params": list(range(len(params)))}
+    return {"state": state, "param_groups": [group]}
+
+
+def adam8_state_from_dict(sd, params, layout, bufs):
+    """Inverse of adam8_state_to_dict: fills the code, absmax and fp32 side buffers in place and returns the step count.  Refuses
+    a state whose moments are not of the dtype this layout holds for the parameter (an fp32 Adam state dict, for one)."""
+    if "state" not in sd or "param_groups" not in sd:
+        raise ValueError("8-bit optimizer: not an 8-bit optimizer state dict (no `state` / `param_groups`)")
+    ids = [i for g in sd["param_groups"] for i in g["params"]]
+    if len(ids) != len(params):
+        raise ValueError(f"optimizer state covers {len(ids)} parameters, the model has {len(params)}")
+    step = 0
+    bufs["state1"].fill_(127)
+    for k in ("state2", "absmax1", "absmax2", "m32", "v32"):
+        bufs[k].zero_()
+    for i, p, (small, off, n, first, nb) in zip(ids, params, layout.params):
+        st = sd["state"].get(i)
+        if st is None:
+            continue
+        if "state1" not in st or "state2" not in st:
+            raise ValueError(f"optimizer state {i}: no `state1` / `state2` (keys {sorted(st)}): not an 8-bit optimizer state")
+        want = torch.float32 if small else torch.uint8
+        for k in ("state1", "state2"):
+            if st[k].dtype != want:
+                raise ValueError(f"optimizer state {i}: {k} is {st[k].dtype}, this trainer holds {want} for a parameter of {n} elements")
+            if tuple(st[k].shape) != tuple(p.shape):
+                raise ValueError(f"optimizer state {i}: {k} shape {tuple(st[k].shape)} != parameter {tuple(p.shape)}")
+        if small:
+            _storage_view(bufs["m32"], first, p).copy_(st["state1"].to(bufs["m32"].device))
+            _storage_view(bufs["v32"], first, p).copy_(st["state2"].to(bufs["v32"].device))
+        else:
+            for k in ("absmax1", "absmax2"):
+                if k not in st or st[k].numel() != nb:
+                    raise ValueError(f"optimizer state {i}: {k} does not hold one value for each of the parameter's {nb} blocks")
+                bufs[k][first:first + nb].copy_(st[k].to(bufs[k].device, torch.float32))
+            _storage_view(bufs["state1"], off, p).copy_(st["state1"].to(bufs["state1"].device))
+            _storage_view(bufs["state2"], off, p).copy_(st["state2"].to(bufs["state2"].device))
+        step = max(step, int(float(st["step"])))
+    return step
+
+
 def lr_lambda(name, num_training_steps, num_warmup_steps=0):
     """diffusers.optimization.get_scheduler multipliers used by the reference: "constant" (main.py) and
     "cosine" (text_to_image LoRA trainer, ddpm_config.py:637); SURVEY A.12."""
@@ -146,7 +261,7 @@ class EMAModel:
         """Re-home the shadow parameters in one flat buffer laid out like model.flat so the EMA update
         fuses into the optimizer pass."""
         flat, _ = model.flat
-        sflat = torch.empty_like(flat)
+        sflat = torch.zeros_like(flat)         # (zeros: the slot padding is never written by the 8-bit optimizer pass)
         off = 0
         new = []
         for s, p in zip(self.shadow_params, model.parameters()):
@@ -229,14 +344,25 @@ class FusedTrainer:
 
     def __init__(self, model, scheduler, ema: EMAModel | None, lr=1e-4, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, adamw=False, max_grad_norm=1.0, loss_sign=1.0, params=None, lr_schedule=None, use_graph=False,
-                 groups=None):
+                 groups=None, optim_bits=32, no_decay=()):
         """`use_graph`: capture add_noise -> forward -> loss -> backward of one step into a hipGraph after `GRAPH_WARMUP` eager steps and
         replay it from then on (the optimizer launch stays eager: its step count and learning rate are host scalars).  For steps that are
         launch-bound on the host - the half-precision SD LoRA step issues ~2 900 short launches - : the same kernels in the same order,
         bit-identical results, no per-launch host work.  Shapes must not change between steps; a capture that fails falls back to eager.
         `groups`: [(slice of the flat buffer, lr multiplier)] - the optimizer runs once per slice at lr * multiplier under ONE clip norm
         over the whole gradient buffer (LoRA+: peft's create_loraplus_optimizer, gad.lora_parameters); slices start on SLOT boundaries.
-        Without it: one launch over the whole buffer, as before."""
+        Without it: one launch over the whole buffer, as before.
+        `optim_bits=8`: bitsandbytes' blockwise 8-bit Adam in place of the fp32 moments (csrc/optim8.hip; `adam8_blocks`): uint8 codes
+        and one absmax per 2048 elements for parameters of at least 4096 elements, fp32 moments for the rest; the weight decay is
+        decoupled and follows the update whatever `adamw` says (Adam8bit and AdamW8bit share that rule), and `no_decay` - one flag per
+        parameter - exempts parameters from it.  Not combined with `groups`."""
+        if optim_bits not in (8, 32):
+            raise ValueError(f"FusedTrainer: optim_bits={optim_bits}: 32 (fp32 moments) or 8 (blockwise 8-bit Adam)")
+        if optim_bits == 8 and groups:
+            raise ValueError("FusedTrainer: optim_bits=8 is not combined with parameter groups (LoRA+ under 8-bit state is not built)")
+        if optim_bits == 32 and len(no_decay):
+            raise ValueError("FusedTrainer: no_decay is a mask of the 8-bit optimizer (optim_bits=8)")
+        self.optim_bits = optim_bits
         self.model, self.scheduler, self.ema = model, scheduler, ema
         self.use_graph, self._graph, self._graph_failed = use_graph, None, False
         if params is None:                      # train everything (DDPM); else only `params` (LoRA: base frozen)
@@ -256,8 +382,18 @@ class FusedTrainer:
                 if sl.start % SLOT or sl.stop % SLOT or not 0 <= sl.start < sl.stop <= self.flat.numel() or sl.step not in (None, 1):
                     raise ValueError(f"FusedTrainer: group {sl} is not a run of whole slots of the flat buffer ({self.flat.numel()} floats)")
         self._sinks_checked, self._unwritten = False, []
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
+        if optim_bits == 8:
+            self.m = self.v = None
+            lay = self.adam8 = adam8_blocks(self.params, weight_decay, no_decay)
+            dev, n = self.flat.device, self.flat.numel()
+            # initial state: every code the zero code (127 signed, 0 unsigned), every absmax 0
+            self.state8 = dict(state1=torch.full((n,), 127, dtype=torch.uint8, device=dev), state2=torch.zeros(n, dtype=torch.uint8, device=dev),
+                               absmax1=torch.zeros(max(1, lay.n_absmax), device=dev), absmax2=torch.zeros(max(1, lay.n_absmax), device=dev),
+                               m32=torch.zeros(max(SLOT, lay.n32), device=dev), v32=torch.zeros(max(SLOT, lay.n32), device=dev))
+            self._blocks8 = torch.from_numpy(lay.table.view("u1").copy()).to(dev)
+        else:
+            self.m = torch.zeros_like(self.flat)
+            self.v = torch.zeros_like(self.flat)
         self.ema_flat = ema.bind_flat(model) if ema is not None else None
         self.hp = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, adamw=adamw)
         self.max_grad_norm, self.loss_sign = max_grad_norm, loss_sign
@@ -363,6 +499,12 @@ class FusedTrainer:
         decay = self.ema.next_decay() if self.ema is not None else 0.0
         if self.lr_schedule is not None:        # LambdaLR semantics: step k (0-based) runs at base_lr * f(k)
             self.hp["lr"] = self.base_lr * self.lr_schedule(self.step_count - 1)
+        if self.optim_bits == 8:
+            s = self.state8
+            ops.clip_adam8_ema_raw(self.flat, self.gflat, self.ema_flat, s["state1"], s["state2"], s["absmax1"], s["absmax2"], s["m32"],
+                                   s["v32"], self._blocks8, sumsq, max_norm=self.max_grad_norm or 0.0, lr=self.hp["lr"],
+                                   betas=self.hp["betas"], eps=self.hp["eps"], step=self.step_count, ema_decay=decay)
+            return
         if self.groups:                         # one clip norm over every gradient, one launch per learning rate
             for sl, mult in self.groups:
                 ops.clip_adam_ema_raw(self.flat[sl], self.gflat[sl], self.m[sl], self.v[sl], None, sumsq, max_norm=self.max_grad_norm or 0.0,
@@ -377,8 +519,14 @@ class FusedTrainer:
 
     def state_dict(self):
         """Optimizer state in torch.optim.Adam's own state_dict format (the `optimizer` entry of
-        ckpt_steps_*.pt, main.py:827-840): the reference can resume it and vice versa."""
+        ckpt_steps_*.pt, main.py:827-840): the reference can resume it and vice versa.  With optim_bits=8: bitsandbytes' key
+        names (`adam8_state_to_dict`)."""
+        if self.optim_bits == 8:
+            return adam8_state_to_dict(self.params, self.adam8, self.state8, self.step_count, self.hp)
         return adam_state_to_torch(self.params, self.m, self.v, self.step_count, self.hp)
 
     def load_state_dict(self, sd):
+        if self.optim_bits == 8:
+            self.step_count = adam8_state_from_dict(sd, self.params, self.adam8, self.state8)
+            return
         self.step_count = adam_state_from_torch(sd, self.params, self.m, self.v)

@@ -51,6 +51,7 @@ def parse_args(argv=None):
     p.add_argument("--adam_beta2", type=float, default=0.999)
     p.add_argument("--adam_weight_decay", type=float, default=1e-2)
     p.add_argument("--adam_epsilon", type=float, default=1e-08)
+    p.add_argument("--use_8bit_adam", action="store_true", help="bitsandbytes' AdamW8bit state (reference :884-892)")
     p.add_argument("--max_grad_norm", type=float, default=1.0)
     p.add_argument("--snr_gamma", type=float, default=None, help="min-SNR loss weighting (reference :319)")
     p.add_argument("--noise_offset", type=float, default=0.0, help="offset noise scale (reference :458)")
@@ -233,7 +234,9 @@ def main(a, backend=None):
                                    lr_schedule=backend.lr_lambda(a.lr_scheduler, max_steps, a.lr_warmup_steps),
                                    # GAD_TRAIN_GRAPH=1: replay the step from a hipGraph (gad.FusedTrainer; for the launch-bound
                                    # half-precision step; the injected test backend does not take the keyword)
-                                   **({"use_graph": True} if os.environ.get("GAD_TRAIN_GRAPH") else {}))
+                                   **({"use_graph": True} if os.environ.get("GAD_TRAIN_GRAPH") else {}),
+                                   # --use_8bit_adam: AdamW8bit, --adam_weight_decay on every LoRA parameter (:884-905)
+                                   **({"optim_bits": 8} if a.use_8bit_adam else {}))
     time_file = os.path.join(model_outdir, "time.csv")
     if not os.path.exists(time_file):
         with open(time_file, "w") as f:

@@ -96,8 +96,9 @@ def split_contributors(args, dataset):
 def main(args, backend=None):
     if backend is None:
         import gad as backend
-    if args.use_8bit_optimizer or args.gradient_accumulation_steps != 1:
-        raise NotImplementedError("the MI355X engine runs the reference default: Adam(W) in fp32, no accumulation")
+    if args.gradient_accumulation_steps != 1:
+        raise NotImplementedError(f"--gradient_accumulation_steps={args.gradient_accumulation_steps}: only 1 is implemented "
+                                  "(the reference's default)")
     if hasattr(backend, "set_operand_precision"):      # --mixed_precision fp16|bf16 -> bf16 operands, fp32 everything else
         backend.set_operand_precision(args.mixed_precision)
     if args.dataset == "celeba" and args.precompute_stage != "reuse":
@@ -154,10 +155,18 @@ def main(args, backend=None):
 
     scheduler = backend.DDPMScheduler(**config["scheduler_config"])
     okw = dict(config["optimizer_config"]["kwargs"])
-    trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
-                                   weight_decay=okw.get("weight_decay", 0.0),
-                                   adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0,
-                                   loss_sign=-1.0 if args.method == "ga" else 1.0)
+    if args.use_8bit_optimizer:
+        # :562-588 bnb.optim.Adam8bit whatever class_name says: the config's decay (KeyError where the config has none, :574) on every
+        # parameter whose name lacks "bias" (get_parameter_names(model, [nn.LayerNorm]): the U-Nets have no LayerNorm), none on the rest
+        trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
+                                       weight_decay=config["optimizer_config"]["kwargs"]["weight_decay"], max_grad_norm=1.0,
+                                       loss_sign=-1.0 if args.method == "ga" else 1.0, optim_bits=8,
+                                       no_decay=["bias" in n for n, _ in model.named_parameters()])
+    else:
+        trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
+                                       weight_decay=okw.get("weight_decay", 0.0),
+                                       adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0,
+                                       loss_sign=-1.0 if args.method == "ga" else 1.0)
     if opt_state is not None:
         trainer.load_state_dict(opt_state)
     loader = backend.DeviceLoader(train_dataset, remaining_idx, batch_size, device)

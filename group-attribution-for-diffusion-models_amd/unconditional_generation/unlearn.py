@@ -215,10 +215,18 @@ def main(args, backend=None):
         model = lora_unlearn(args, backend, config, dataset, model, ema_model, scheduler, remaining_idx)
     else:
         okw = dict(config["optimizer_config"]["kwargs"])
-        trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
-                                       weight_decay=okw.get("weight_decay", 0.0),
-                                       adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0,
-                                       loss_sign=-1.0 if args.method.startswith("ga") else 1.0)
+        if args.use_8bit_optimizer:
+            # :429-477 bnb.optim.Adam8bit whatever class_name says: the config's decay (KeyError where the config has none, :459) on
+            # every parameter whose name lacks "bias", none on the rest
+            trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
+                                           weight_decay=config["optimizer_config"]["kwargs"]["weight_decay"], max_grad_norm=1.0,
+                                           loss_sign=-1.0 if args.method.startswith("ga") else 1.0, optim_bits=8,
+                                           no_decay=["bias" in n for n, _ in model.named_parameters()])
+        else:
+            trainer = backend.FusedTrainer(model, scheduler, ema_model, lr=okw.get("lr", 1e-4),
+                                           weight_decay=okw.get("weight_decay", 0.0),
+                                           adamw=config["optimizer_config"]["class_name"] == "AdamW", max_grad_norm=1.0,
+                                           loss_sign=-1.0 if args.method.startswith("ga") else 1.0)
         loader = backend.DeviceLoader(dataset, remaining_idx, config["batch_size"], device)
         n_t = scheduler.config.num_train_timesteps
         steps_goal = args.gd_steps if args.method.startswith("gd") else int(config["training_steps"]["ga"] // args.ga_ratio)

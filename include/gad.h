@@ -404,6 +404,45 @@ int gad_clip_adam_ema(const gad_adam_args* a, void* stream);
 /* standalone EMAModel.step (diffusers training_utils; main.py:725): ema -= (1-decay) * (ema - p) */
 int gad_ema_update(float* ema, const float* p, int64_t n, float decay, void* stream);
 
+/* ------------------------------------------------------------------------------
+ * 8-bit blockwise Adam over the flat parameter buffer (csrc/optim8.hip): bitsandbytes' Adam8bit / AdamW8bit
+ * (main.py:562-588, unlearn.py:429-477, train_text_to_image_lora.py:884-892) restated - blocks of 2048 elements, parameters
+ * below 4096 elements keep fp32 moments, no percentile clipping - fused with the clip and the EMA like gad_clip_adam_ema.
+ *   gad_adam8_qmap: the 256 ascending fp32 code values of the signed (first moment; zero at index 127) or unsigned (second
+ *     moment; zero at index 0) dynamic map, into a HOST array; needs no GPU.  The kernel's tables are the same constants.
+ *   gad_adam8_block: one run of at most 2048 elements of ONE parameter.  Blocks never cross a parameter and never cover the
+ *     padding between parameters.  `state` is the block's index into absmax1 / absmax2, or with `fp32` set the offset of its
+ *     moments in m32 / v32 (a multiple of 4).  `offset` is a multiple of 8.
+ *   gad_clip_adam8_ema, per element, in fp32: g *= coef (as gad_clip_adam_ema) ; m = qmap1[c1]*absmax1[b], v = qmap2[c2]*absmax2[b] ;
+ *     m = m*beta1 + (1-beta1) g ; v = v*beta2 + (1-beta2) g g ; p -= (lr sqrt(1-beta2^t)/(1-beta1^t)) m / (sqrt(v) + eps sqrt(1-beta2^t)) ;
+ *     p *= 1 - lr*weight_decay if the block's weight_decay > 0 ; EMA as gad_clip_adam_ema ; absmax1[b] = max|m|, absmax2[b] = max v ;
+ *     codes = nearest map value of m/absmax1, v/absmax2 (lower index on a tie; a negative m never takes the zero code: 126);
+ *     a block whose absmax is 0 stores the zero code.  A descriptor that points outside n / n32 / n_absmax is skipped.
+ * ---------------------------------------------------------------------------- */
+int gad_adam8_qmap(int is_signed, float* out256);
+typedef struct gad_adam8_block {
+  int64_t offset;           /* first element in the flat buffer                                 */
+  int32_t len;              /* 1..2048                                                          */
+  int32_t state;            /* absmax index, or offset into m32 / v32 if fp32                   */
+  float weight_decay;       /* decoupled, applied after the update; 0 = none                    */
+  int32_t fp32;             /* 1: the parameter keeps fp32 moments (fewer than 4096 elements)   */
+} gad_adam8_block;
+typedef struct gad_adam8_args {
+  float* p; const float* g; float* ema;       /* flat buffers of n floats; ema may be NULL      */
+  uint8_t* state1; uint8_t* state2;           /* n code bytes each, laid out like p             */
+  float* absmax1; float* absmax2;             /* n_absmax floats each                           */
+  float* m32; float* v32;                     /* n32 floats each: moments of the small parameters */
+  const gad_adam8_block* blocks;              /* DEVICE table of n_blocks descriptors           */
+  int64_t n, n32;
+  int32_t n_absmax, n_blocks;
+  const float* sumsq;       /* device scalar from gad_sumsq, or NULL for no clipping            */
+  float max_norm;
+  float lr, beta1, beta2, eps;
+  int32_t step;             /* 1-based                                                          */
+  float ema_decay;
+} gad_adam8_args;
+int gad_clip_adam8_ema(const gad_adam8_args* a, void* stream);
+
 
 /* ==============================================================================
  * Half-precision activation path ("--mixed_precision fp16|bf16" of the reference's Stable-Diffusion jobs:
