@@ -1,5 +1,6 @@
 // Device primitives every kernel file shares (gfx950 only), each written once: the LDS-DMA issue, the s_waitcnt encodings and
-// the barriers built on them, the zero block, the XCD-aware block remap, Philox, and the small arithmetic helpers.
+// the barriers built on them, the zero block, the XCD-aware block remap, Philox with its uniform and Box-Muller maps, and the
+// small arithmetic helpers.
 // A kernel file does not call the DMA builtin or write a s_waitcnt immediate itself: it uses these.
 #pragma once
 #include "gad_common.h"
@@ -83,6 +84,23 @@ __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint32_t k0, uint32_t k1
     k1 += 0xBB67AE85u;
   }
   return c;
+}
+
+// u = (x + 1/2) 2^-32 in (0, 1]: fl32(fl32(x) * 2^-32 + 2^-33), one fma (the restatement in tests/ does the same in fp64)
+__device__ __forceinline__ float jl_uniform(uint32_t x) {
+  return __builtin_fmaf((float)x, 0x1p-32f, 0x1p-33f);
+}
+
+// one Philox block -> four standard normals: Box-Muller on (u0, u1) and (u2, u3), in the order cos, sin, cos, sin
+// (the projector's normal entries and the DDPM step's variance noise)
+__device__ __forceinline__ void jl_normal4(uint4 x, float b[4]) {
+  const float r01 = sqrtf(-2.0f * logf(jl_uniform(x.x)));
+  const float r23 = sqrtf(-2.0f * logf(jl_uniform(x.z)));
+  const float h1 = 2.0f * jl_uniform(x.y), h3 = 2.0f * jl_uniform(x.w);
+  b[0] = r01 * cospif(h1);
+  b[1] = r01 * sinpif(h1);
+  b[2] = r23 * cospif(h3);
+  b[3] = r23 * sinpif(h3);
 }
 
 // exact-fp32 16x16 MFMA step (k = 4)

@@ -40,22 +40,11 @@ Plan jl_plan(int64_t P, int32_t d) {
   return pl;
 }
 
-// u = (x + 1/2) 2^-32 in (0, 1]: fl32(fl32(x) * 2^-32 + 2^-33), one fma (the restatement in tests/ does the same in fp64)
-__device__ __forceinline__ float jl_uniform(uint32_t x) {
-  return __builtin_fmaf((float)x, 0x1p-32f, 0x1p-33f);
-}
-
+// the uniform map and the four normals of a Philox block: jl_uniform / jl_normal4 in gad_dev.h
 template <int TYPE>
 __device__ __forceinline__ void jl_entries(uint64_t row, uint32_t ct, int j, uint32_t k0, uint32_t k1, float b[4]) {
   if constexpr (TYPE == GAD_JL_NORMAL) {
-    const uint4 x = philox4x32_10(make_uint4(ct * 16u + (uint32_t)j, (uint32_t)row, (uint32_t)(row >> 32), 0u), k0, k1);
-    const float r01 = sqrtf(-2.0f * logf(jl_uniform(x.x)));
-    const float r23 = sqrtf(-2.0f * logf(jl_uniform(x.z)));
-    const float h1 = 2.0f * jl_uniform(x.y), h3 = 2.0f * jl_uniform(x.w);
-    b[0] = r01 * cospif(h1);
-    b[1] = r01 * sinpif(h1);
-    b[2] = r23 * cospif(h3);
-    b[3] = r23 * sinpif(h3);
+    jl_normal4(philox4x32_10(make_uint4(ct * 16u + (uint32_t)j, (uint32_t)row, (uint32_t)(row >> 32), 0u), k0, k1), b);
   } else {
     const uint4 x = philox4x32_10(make_uint4(ct >> 1, (uint32_t)row, (uint32_t)(row >> 32), 1u), k0, k1);
     const uint32_t lo = (ct & 1) ? x.z : x.x, hi = (ct & 1) ? x.w : x.y;

@@ -1652,6 +1652,29 @@ def ddim_step_raw(x, eps, alpha_t: float, alpha_prev: float, clip: float, out=No
     return out
 
 
+_DDPM_VARIANCE = {"fixed_small": _capi.DDPM_FIXED_SMALL, "fixed_large": _capi.DDPM_FIXED_LARGE}
+
+
+def ddpm_step_raw(x, eps, seeds, t: int, alpha_t: float, alpha_prev: float, clip: float, variance_type="fixed_small", out=None):
+    """Ancestral DDPM update of a batch in one launch (gad_ddpm_step): x, eps [B][...] fp32, seeds [B] int64 device (row b's
+    64-bit noise key).  Row b's variance noise is a function of (seeds[b], t, element) alone.  `out` may be x (in place)."""
+    _req(x, "ddpm x")
+    _req(eps, "ddpm eps")
+    if variance_type not in _DDPM_VARIANCE:
+        raise _capi.GadError(f"ddpm_step: variance_type={variance_type!r}, expected fixed_small or fixed_large")
+    B = x.shape[0]
+    if eps.shape != x.shape or not (seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() and seeds.numel() == B):
+        raise _capi.GadError(f"ddpm_step: eps {tuple(eps.shape)} must match x {tuple(x.shape)} and seeds must be a contiguous "
+                             f"int64 device tensor of {B} entries, got {seeds.dtype} {seeds.device} {tuple(seeds.shape)}")
+    out = torch.empty_like(x) if out is None else _req(out, "ddpm out")
+    if out.shape != x.shape:
+        raise _capi.GadError(f"ddpm_step: out {tuple(out.shape)} must match x {tuple(x.shape)}")
+    check(_capi.load().gad_ddpm_step(x.data_ptr(), eps.data_ptr(), out.data_ptr(), B, x.numel() // max(B, 1), seeds.data_ptr(),
+                                     int(t), alpha_t, alpha_prev, clip, _DDPM_VARIANCE[variance_type], _stream()),
+          "gad_ddpm_step")
+    return out
+
+
 def to_image01_raw(x):
     _req(x, "to_image01 x")
     y = torch.empty_like(x)

@@ -14,7 +14,11 @@ permutation of rows (and the zero padding contributes nothing).
 vmap(grad(f)) yields the per-sample gradients of a batch): with bf16 activations every LoRA gradient is a contraction over
 the token axis, so ONE ordinary forward / backward over S samples x j timesteps writes all S per-sample gradients into S
 staging rows (half.per_sample_gradients -> gad_hgemm_tn_seg); with fp32 activations it runs one sample per backward
-through the flat buffer, as `gradient_features` does."""
+through the flat buffer, as `gradient_features` does.
+
+`journey_latents` / `journey_gradient_features` are Journey-TRAK's validation side (d_trak_grad.py --calculate_gen_grad, reference
+:450-494, :729-731): batched ancestral DDPM trajectories stepped by gad_ddpm_step (csrc/ddpm.hip: one launch per step, variance
+noise from in-kernel Philox keyed per sample), and the features of their latents taken as they are through the same _GradStep."""
 from __future__ import annotations
 
 import ctypes as C
@@ -122,7 +126,8 @@ def _seed_gradient(pred, behaviour):
 
 
 class _GradStep:
-    """add_noise -> U-Net -> behaviour (+ its gradient) -> backward into the flat gradient buffer of `model`"""
+    """(add_noise ->) U-Net -> behaviour (+ its gradient) -> backward into the flat gradient buffer of `model`.
+    `add_noise=False` feeds x to the U-Net as it is (Journey-TRAK: x is a latent of the generation trajectory)."""
 
     def __init__(self, model, scheduler, behaviour):
         if behaviour not in BEHAVIOURS:
@@ -132,8 +137,8 @@ class _GradStep:
         self.params = list(model.parameters())
         self._unwritten = None
 
-    def __call__(self, x, noise, t):
-        noisy = self.scheduler.add_noise(x, noise, t)
+    def __call__(self, x, noise, t, add_noise=True):
+        noisy = self.scheduler.add_noise(x, noise, t) if add_noise else x
         pred = self.model(noisy, t).sample.contiguous()
         if self.behaviour == "loss":                              # TRAK: MSE(pred, eps)
             _, d = ops.mse_fwd_bwd_raw(pred, noise.contiguous())
@@ -172,6 +177,15 @@ def gradient_features(model, scheduler, images, behaviour, timesteps, projector:
     eval mode (vmap's default randomness='error' forces the same in the reference).  Rows are staged in a
     [projector.max_batch_size][P] buffer and every full buffer is projected with one launch.  `out`: an optional host
     array (e.g. np.memmap) that receives each projected block as it is done; the features are returned as a CPU tensor."""
+    return _feature_rows(model, scheduler, images, behaviour, timesteps, projector, opt_seed, batch_size, model_id, out,
+                         as_is=False, scale=1.0)
+
+
+def _feature_rows(model, scheduler, images, behaviour, timesteps, projector, opt_seed, batch_size, model_id, out, as_is, scale):
+    """The body of gradient_features and journey_gradient_features.  as_is=False: images [N][C][H][W], a sample's k rows are its
+    image noised at the k timesteps.  as_is=True: images [N][>= k][C][H][W], its k rows are images[i][:k], fed to the U-Net as
+    they are.  Either way the noise draw (the `loss` target) follows the reference's rule, and the staged row is `scale` x the
+    mean over the k rows of grad f."""
     from .coalition import seed_everything
     dev = projector.device
     step = _GradStep(model, scheduler, behaviour)
@@ -201,15 +215,19 @@ def gradient_features(model, scheduler, images, behaviour, timesteps, projector:
     try:
         for b0 in range(0, N, batch_size):
             image = images[b0:b0 + batch_size].to(dev, torch.float32)
+            like = torch.empty((image.shape[0],) + tuple(image.shape[-3:]), device=dev)   # the reference's batch: [bsz][C][H][W]
             noises = []
             for t in timesteps:
                 seed_everything(opt_seed * 1000 + t)
-                noises.append(torch.randn_like(image))
+                noises.append(torch.randn_like(like))
             noise = torch.stack(noises, dim=1)                   # [bsz][k][C][H][W]
             for i in range(image.shape[0]):
-                x = image[i:i + 1].expand(k, *image.shape[1:]).contiguous()
-                gflat = step(x, noise[i].contiguous(), ts)
-                staging[filled].copy_(gflat)
+                x = image[i, :k].contiguous() if as_is else image[i:i + 1].expand(k, *image.shape[1:]).contiguous()
+                gflat = step(x, noise[i].contiguous(), ts, add_noise=not as_is)
+                if scale == 1.0:
+                    staging[filled].copy_(gflat)
+                else:
+                    torch.mul(gflat, scale, out=staging[filled])
                 filled += 1
                 if filled == G:
                     flush()
@@ -218,6 +236,89 @@ def gradient_features(model, scheduler, images, behaviour, timesteps, projector:
     finally:
         model.train(was_training)
     return feats
+
+
+def journey_timesteps(k_partition, num_train_timesteps=1000):
+    """The timesteps a Journey-TRAK trajectory visits (d_trak_grad.py:472): T - 1 downwards in strides of T // k.  Their
+    count is ceil(T / (T // k)), which is k only when k divides T (k = 3: [999, 666, 333, 0])."""
+    T = int(num_train_timesteps)
+    return list(range(T - 1, -1, -(T // int(k_partition))))
+
+
+def journey_seeds(opt_seed, samples):
+    """The 64-bit noise key of every sample, (opt_seed << 32) | sample, as int64 values (two's complement)"""
+    keys = [((int(opt_seed) & 0xFFFFFFFF) << 32) | (int(s) & 0xFFFFFFFF) for s in samples]
+    return [v - (1 << 64) if v >= 1 << 63 else v for v in keys]
+
+
+@torch.no_grad()
+def journey_latents(model, scheduler, n_samples, k_partition, opt_seed=42, batch_size=64, posterior_steps=100, device=None):
+    """[n_samples][K][C][H][W] (CPU): the latents of n_samples ancestral DDPM trajectories (d_trak_grad.py:450-483), K =
+    len(journey_timesteps(k_partition)).
+
+    As in the reference (:481), index j of a row is the latent that ENTERED the U-Net at journey_timesteps[K - 1 - j]: index
+    K - 1 is the initial noise, and index 0 is the input of the last visited timestep - not a finished image (the reference's
+    last forward and step produce a tensor it never stores, so only K - 1 forwards and steps are run here).  Row s starts from
+    torch.randn((1, C, H, W), generator=torch.Generator(device).manual_seed(s), device=device), the reference's per-sample
+    seeded draw.  The posterior of a step at t is taken towards prev_t = t - T // posterior_steps (abar_prev = 1 when
+    prev_t < 0): the reference sets num_inference_steps = 100 whatever k_partition is (:455-456), and the default keeps that.
+
+    Deliberate deviation: the variance noise of row s is keyed by (opt_seed << 32) | s and generated inside gad_ddpm_step
+    (Philox, counter (element >> 2, t, 0, 2)), so a trajectory is reproducible and does not depend on batch_size or on the
+    rows it shares a launch with; the reference draws it from the unseeded global generator.  Rows run in batches of
+    `batch_size` through a device slab [K][rows][C][H][W]: the U-Net reads slice i and the step writes slice i + 1."""
+    c = scheduler.config
+    if c.prediction_type != "epsilon" or c.thresholding or c.variance_type not in ops._DDPM_VARIANCE:
+        raise NotImplementedError("journey_latents: epsilon prediction with fixed_small / fixed_large variance only")
+    dev = torch.device(device) if device is not None else next(model.parameters()).device
+    T = int(c.num_train_timesteps)
+    ts = journey_timesteps(k_partition, T)
+    K = len(ts)
+    stride = T // int(posterior_steps)
+    clip = float(c.clip_sample_range) if c.clip_sample else 0.0
+    ac = scheduler.alphas_cumprod
+    ss = model.config.sample_size
+    H, W = ss if isinstance(ss, (tuple, list)) else (ss, ss)
+    C_in = model.config.in_channels
+    rows = max(1, min(int(batch_size), int(n_samples)))
+    slab = torch.empty(K, rows, C_in, H, W, device=dev)
+    tdev = torch.empty(rows, device=dev, dtype=torch.int64)
+    out = torch.empty(n_samples, K, C_in, H, W)
+    was_training = model.training
+    model.eval()
+    try:
+        for s0 in range(0, n_samples, rows):
+            n = min(rows, n_samples - s0)
+            for r in range(n):
+                slab[0, r] = torch.randn((1, C_in, H, W), generator=torch.Generator(dev).manual_seed(s0 + r), device=dev)[0]
+            seeds = torch.tensor(journey_seeds(opt_seed, range(s0, s0 + n)), dtype=torch.int64, device=dev)
+            for i, t in enumerate(ts[:-1]):
+                tdev.fill_(t)
+                eps = model(slab[i, :n], tdev[:n]).sample.contiguous()
+                prev_t = t - stride
+                ops.ddpm_step_raw(slab[i, :n], eps, seeds, t, ac[t].item(), ac[prev_t].item() if prev_t >= 0 else 1.0, clip,
+                                  c.variance_type, out=slab[i + 1, :n])
+            out[s0:s0 + n] = slab[:, :n].flip(0).transpose(0, 1).cpu()
+    finally:
+        model.train(was_training)
+    return out
+
+
+def journey_gradient_features(model, scheduler, latents, behaviour, timesteps, projector: Projector, opt_seed=42, batch_size=8,
+                              model_id=0, out=None, k_partition=None):
+    """[N][proj_dim] Journey-TRAK features of the trajectories `latents` [N][K][C][H][W] (journey_latents); gradient_features'
+    contract otherwise.  Row i's k = len(timesteps) rows are latents[i][index_t] evaluated at timesteps[index_t] as they are -
+    no add_noise (d_trak_grad.py:729-731).  The `loss` target is the noise drawn by gradient_features' rule
+    (seed_everything(opt_seed * 1000 + t), one draw of the data batch's [bsz][C][H][W]).  The sum over the rows is divided by
+    `k_partition` as the reference does (:770), not by the number of rows (they differ when k does not divide T); None: k.
+
+    Kept from the reference: with --t_strategy uniform the gradient at index j is taken at t = j (T // k), while the latent at
+    index j entered the U-Net at journey_timesteps[K - 1 - j] = j (T // k) + (T // k - 1) when k divides T."""
+    k = len(timesteps)
+    if latents.dim() != 5 or latents.shape[1] < k:
+        raise ValueError(f"latents {tuple(latents.shape)}: expected [N][K >= {k}][C][H][W]")
+    return _feature_rows(model, scheduler, latents, behaviour, timesteps, projector, opt_seed, batch_size, model_id, out,
+                         as_is=True, scale=k / float(k_partition if k_partition is not None else k))
 
 
 def _per_row_seed(pred, target, behaviour):

@@ -1,4 +1,4 @@
-"""Scores from projected gradient features: D-TRAK, TRAK, relative / renormalized IF, vanilla gradient
+"""Scores from projected gradient features: D-TRAK, TRAK, Journey-TRAK, relative / renormalized IF, vanilla gradient
 (entry point kept from the reference src/attributions/methods/compute_gradient_score.py).
 
 Host linear algebra in fp64 (a [d][d] kernel, d = 1024 by default: milliseconds, not a device kernel).  The features
@@ -67,13 +67,22 @@ def _n_images(sample_dir):
 def compute_gradient_scores(args, retraining=False, training_seeds=None):
     """Compute scores for D-TRAK, TRAK, and influence function (compute_gradient_score.py:13-136)."""
     dataset = create_dataset(dataset_name=args.dataset, train=True)
-    if args.gradient_type == "journey_trak":
-        raise NotImplementedError("journey_trak needs the generation gradients (--calculate_gen_grad), not ported")
     model_behavior = "mean-squared-l2-norm" if args.gradient_type == "d_trak" else "loss"
     t_strategy = "uniform"
     tag = f"f={model_behavior}_t={t_strategy}_k={args.k_partition}_d={args.projector_dim}"
-    val_grad_path = os.path.join(args.sample_dir, "d_trak", f"reference_{tag}")
-    val_phi = np.memmap(val_grad_path, dtype=np.float32, mode="r", shape=(_n_images(args.sample_dir), args.projector_dim))
+    if args.gradient_type == "journey_trak":
+        # the generation gradients of d_trak_grad.py --calculate_gen_grad (:26-33, :42): sample_size rows, no --sample_dir;
+        # train side, kernel, formula and aggregation are trak's
+        val_grad_path = os.path.join(constants.OUTDIR, args.dataset, "d_trak", "full", f"gen_{tag}")
+        have = os.path.getsize(val_grad_path) // (4 * args.projector_dim)
+        if args.sample_size is None or have < args.sample_size:
+            raise ValueError(f"journey_trak: {val_grad_path} holds {have} rows of {args.projector_dim} features, "
+                             f"sample_size={args.sample_size} asked for")
+        n_val = args.sample_size
+    else:
+        val_grad_path = os.path.join(args.sample_dir, "d_trak", f"reference_{tag}")
+        n_val = _n_images(args.sample_dir)
+    val_phi = np.memmap(val_grad_path, dtype=np.float32, mode="r", shape=(n_val, args.projector_dim))
     val_phi = val_phi[: args.sample_size]
 
     if retraining:

@@ -5,9 +5,13 @@ reference writes it.  The features come from gad.trak: one fused forward / backw
 and the HIP random projector in place of trak's CudaProjector.
 
 Deliberate deviation: rows are written in dataset order (row r = r-th remaining training image, or the r-th sample
-image in sorted file order); the reference writes them in the order of a shuffled DataLoader.  Not ported (refused by
-name): --calculate_gen_grad (Journey-TRAK generation gradients), the celeba / imagenette latent pipelines, and the
-behaviours ssim / fid / nrmse / is."""
+image in sorted file order); the reference writes them in the order of a shuffled DataLoader.
+
+--calculate_gen_grad (Journey-TRAK, reference :450-494) generates --n_samples ancestral DDPM trajectories with
+gad.trak.journey_latents (one fused gad_ddpm_step launch per step, variance noise keyed by (opt_seed, sample): a rerun is
+bit-identical, where the reference draws that noise from an unseeded generator) and writes the features of their latents
+to the gen_ path.  Not ported (refused by name): --calculate_gen_grad together with --sample_dir, the celeba / imagenette
+latent pipelines, and the behaviours ssim / fid / nrmse / is."""
 import argparse
 import os
 import sys
@@ -127,22 +131,32 @@ def main(args, backend=None):
     """Compute and save the projected gradient features (d_trak_grad.py:184-696)."""
     if backend is None:
         import gad as backend
-    from gad.trak import Projector, ProjectionType, gradient_features, selected_timesteps
+    from gad.trak import (Projector, ProjectionType, gradient_features, journey_gradient_features, journey_latents,
+                          selected_timesteps)
     from src.diffusion_utils import build_model, dataset_config
     from src.utils import get_max_steps
 
-    if args.calculate_gen_grad:
-        raise NotImplementedError("--calculate_gen_grad (Journey-TRAK generation gradients) is not ported")
+    if args.calculate_gen_grad and args.sample_dir is not None:
+        raise NotImplementedError("--calculate_gen_grad with --sample_dir: calculate_gen_grad generates its own validation "
+                                  "set (the combination is meaningless in the reference)")
     if args.dataset in ("celeba", "imagenette"):
         raise NotImplementedError(f"--dataset {args.dataset}: the latent (VQ-VAE / LDM) gradient features are not ported")
+    if args.calculate_gen_grad:
+        for flag in ("n_samples", "k_partition", "t_strategy"):
+            if getattr(args, flag) is None:
+                raise ValueError(f"--calculate_gen_grad requires --{flag}")
+        if args.n_samples < 1:
+            raise ValueError(f"--n_samples {args.n_samples}: must be >= 1")
     if args.t_strategy is None or args.k_partition is None:
         raise ValueError("--t_strategy and --k_partition are required")
     device = torch.device(args.device)
     config = dataset_config(args.dataset)
     batch_size = 8                                                     # config["batch_size"] = 8 (:326)
 
-    train_dataset = create_dataset(dataset_name=args.dataset, train=True)
-    if args.sample_dir is None:
+    train_dataset = None if args.calculate_gen_grad else create_dataset(dataset_name=args.dataset, train=True)
+    if args.calculate_gen_grad:
+        images, n_samples = None, args.n_samples                       # the validation set is generated below
+    elif args.sample_dir is None:
         n_samples = len(train_dataset)
         backend.seed_everything(args.opt_seed)                         # the training transform's random flips
         images = torch.stack([torch.as_tensor(train_dataset[int(i)][0]) for i in remaining_indices(args, train_dataset)])
@@ -168,11 +182,16 @@ def main(args, backend=None):
     projector = Projector(grad_dim=gflat.numel(), proj_dim=args.projector_dim, seed=args.opt_seed,
                           proj_type=ProjectionType.normal, device=device, max_batch_size=32)
     dstore_keys = np.memmap(out_path, dtype=np.float32, mode="w+", shape=(n_samples, args.projector_dim))
-    gradient_features(model, scheduler, images, args.model_behavior,
-                      selected_timesteps(args.t_strategy, args.k_partition, scheduler.config.num_train_timesteps),
-                      projector, opt_seed=args.opt_seed, batch_size=batch_size, out=dstore_keys)
+    timesteps = selected_timesteps(args.t_strategy, args.k_partition, scheduler.config.num_train_timesteps)
+    if args.calculate_gen_grad:                                        # Journey-TRAK (d_trak_grad.py:450-494, :729-731)
+        latents = journey_latents(model, scheduler, n_samples, args.k_partition, opt_seed=args.opt_seed, device=device)
+        journey_gradient_features(model, scheduler, latents, args.model_behavior, timesteps, projector, opt_seed=args.opt_seed,
+                                  batch_size=batch_size, out=dstore_keys, k_partition=args.k_partition)
+    else:
+        gradient_features(model, scheduler, images, args.model_behavior, timesteps, projector, opt_seed=args.opt_seed,
+                          batch_size=batch_size, out=dstore_keys)
     dstore_keys.flush()
-    print(f"saved {len(images)} x {args.projector_dim} features to {out_path}")
+    print(f"saved {n_samples if images is None else len(images)} x {args.projector_dim} features to {out_path}")
     return out_path
 
 

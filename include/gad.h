@@ -598,6 +598,31 @@ int64_t gad_jl_project_workspace_bytes(const gad_jl_args* a);
 int gad_jl_project(const gad_jl_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * Ancestral DDPM update with in-kernel variance noise (csrc/ddpm.hip): the scheduler.step of the Journey-TRAK
+ * trajectory generator (reference src/attributions/methods/d_trak_grad.py:472-479, diffusers DDPMScheduler.step with
+ * epsilon prediction).  x, eps, x_prev: B rows of n contiguous floats.  Per element, with cur_alpha = alpha_t / alpha_prev:
+ *   x0     = (x - sqrt(1 - alpha_t) eps) / sqrt(alpha_t), clamped to +-clip when clip > 0
+ *   mean   = sqrt(alpha_prev) (1 - cur_alpha) / (1 - alpha_t) x0 + sqrt(cur_alpha) (1 - alpha_prev) / (1 - alpha_t) x
+ *   x_prev = mean + sqrt(var) z   for t > 0      GAD_DDPM_FIXED_SMALL  var = max((1 - alpha_prev) / (1 - alpha_t) (1 - cur_alpha), 1e-20)
+ *                                                GAD_DDPM_FIXED_LARGE  var = 1 - cur_alpha
+ *   x_prev = mean                 for t == 0     (Philox is not called, seeds is not read)
+ * The coefficients are formed in fp64 on the host from the two fp32 alphas and rounded once to fp32.
+ * z is never stored: element e of row b takes word e & 3 of one Philox-4x32-10 call (Random123 constants) with
+ *   key     (seeds[b] low 32 bits, seeds[b] high 32 bits)
+ *   counter (e >> 2, t, 0, 2)
+ * through the projector's maps: words x -> u = fl32(fl32(x) * 2^-32 + 2^-33), Box-Muller on (u0,u1), (u2,u3) in the order
+ * r01 cos, r01 sin, r23 cos, r23 sin with r = sqrt(-2 ln u_even) and angle 2 pi u_odd.  A row's result is a function of
+ * (seeds[b], t, the row's own x and eps) alone: it does not depend on B, on the row's position or on the launch grid, and a
+ * repeated launch gives equal bits.  x and eps are read once and x_prev written once (12 B per element); no workspace, no
+ * atomics; x_prev == x (in place) is allowed.  Refused with a named error before any HIP call: a null pointer, a base that
+ * is not 16-byte aligned (seeds: 8-byte), n % 4 != 0, n / 4 > 2^32, B <= 0, t < 0, an alpha outside (0, 1],
+ * alpha_prev < alpha_t, clip < 0, an unknown variance_type.
+ * ---------------------------------------------------------------------------- */
+enum gad_ddpm_variance { GAD_DDPM_FIXED_SMALL = 0, GAD_DDPM_FIXED_LARGE = 1 };
+int gad_ddpm_step(const float* x, const float* eps, float* x_prev, int32_t B, int64_t n, const int64_t* seeds, int32_t t,
+                  float alpha_t, float alpha_prev, float clip, int32_t variance_type, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Local model behaviours of the unconditional models (csrc/local.hip; reference
  * unconditional_generation/unlearn.py:871-948, calculate_local_scores.py:303-374).
  * All three are order-deterministic (no atomics): a result depends on its own image / segment and on the
