@@ -88,7 +88,7 @@ class CelebaCycle(_EntryPointCycle):
 class SDLoRACycle(_EntryPointCycle):
     """BASELINE configs 4 / 5.  `train_args`: the train_text_to_image_lora.py flags shared by every coalition (data dir,
     output dir, --method, --lora_dir / --lora_steps of the starting LoRA, --max_train_steps 200 ...); `behaviour_args`:
-    the compute_model_behaviors.py flags (--reference_lora_dir, --num_images, --resolution, ...)."""
+    the compute_model_behaviors.py flags (--reference_lora_dir, --num_images, --resolution, --sampler, ...)."""
     extra_keys = ["aesthetic_score_0.5", "aesthetic_score_0.75", "aesthetic_score_0.9", "aesthetic_score_avg",
                   "clip_prompt_score_0.5", "clip_prompt_score_0.75", "clip_prompt_score_0.9", "clip_prompt_score_avg"]
 

@@ -1675,6 +1675,37 @@ def ddpm_step_raw(x, eps, seeds, t: int, alpha_t: float, alpha_prev: float, clip
     return out
 
 
+def plms_step_raw(x, eps, cs: float, cm: float, weights, history=(), push=None, x_saved=None, saved_mode=_capi.PLMS_SAVED_NONE,
+                  guidance=None, out=None):
+    """One PLMS step in one launch (gad_plms_step): x fp32, eps the U-Net output - of the doubled batch [uncond ; cond] when
+    `guidance` is a number, of x's own shape when it is None.  `weights` = (w0, w1, w2, w3) for (e, *history), `history` the stored
+    predictions newest first (at most three); `push` receives e; `x_saved` is written (PLMS_SAVE) or takes x's place
+    (PLMS_USE_SAVED).  cs, cm and the weights are python floats (fp64), rounded once in the entry point.  `out` may be x."""
+    _req(x, "plms x")
+    _req(eps, "plms eps")
+    n = x.numel()
+    if eps.numel() != (n if guidance is None else 2 * n):
+        raise _capi.GadError(f"plms_step: eps has {eps.numel()} elements, expected "
+                             + (f"{n} (x's own)" if guidance is None else f"{2 * n} (the doubled batch [uncond ; cond])"))
+    history = tuple(history)
+    w = tuple(float(v) for v in weights)
+    if len(w) != 4 or len(history) > 3:
+        raise _capi.GadError(f"plms_step: {len(w)} weights and {len(history)} history terms, expected 4 and at most 3")
+    for name, t in [(f"plms h{i + 1}", h) for i, h in enumerate(history)] + [("plms push", push), ("plms x_saved", x_saved)]:
+        if t is not None and _req(t, name).numel() != n:
+            raise _capi.GadError(f"plms_step: {name[5:]} has {t.numel()} elements, x has {n}")
+    out = torch.empty_like(x) if out is None else _req(out, "plms out")
+    if out.numel() != n:
+        raise _capi.GadError(f"plms_step: out {tuple(out.shape)} must match x {tuple(x.shape)}")
+    h = [t.data_ptr() for t in history] + [None] * (3 - len(history))
+    eps_c = None if guidance is None else eps.data_ptr() + 4 * n
+    check(_capi.load().gad_plms_step(x.data_ptr(), eps.data_ptr(), eps_c, 0.0 if guidance is None else float(guidance), h[0], h[1],
+                                     h[2], None if push is None else push.data_ptr(),
+                                     None if x_saved is None else x_saved.data_ptr(), int(saved_mode), out.data_ptr(), n,
+                                     float(cs), float(cm), w[0], w[1], w[2], w[3], _stream()), "gad_plms_step")
+    return out
+
+
 def to_image01_raw(x):
     _req(x, "to_image01 x")
     y = torch.empty_like(x)

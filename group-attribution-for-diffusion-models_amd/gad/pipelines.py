@@ -13,7 +13,7 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, PNDMScheduler
 
 
 class DDPMPipeline:
@@ -162,14 +162,14 @@ class StableDiffusionLatentPipeline:
     (text_to_image/compute_model_behaviors.py:311-326): classifier-free guidance on a doubled batch and the
     scheduler update, returning LATENTS.  The VAE decoder and the CLIP text encoder (hub-fetched, frozen,
     off the hot path) stay outside: the caller passes prompt / negative-prompt embeddings and decodes.
-    Scheduler: DDIM over the SD beta schedule (the sampler class shipped with miniSD is unknown offline,
-    SURVEY A.13, so it is a parameter)."""
+    Scheduler: the sampler class shipped with miniSD is unknown offline, so it is a parameter - a DDIMScheduler
+    (the default, `sd_scheduler("ddim")`: one gad_cfg_ddim_step per step) or a PNDMScheduler (`sd_scheduler("pndm")`, what
+    SD-1.x repositories normally ship: len(timesteps) = num_inference_steps + 1 U-Net calls, one gad_plms_step each)."""
 
     def __init__(self, unet, scheduler=None):
-        from .schedulers import DDIMScheduler
+        from .schedulers import sd_scheduler
         self.unet = unet
-        self.scheduler = scheduler or DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
-                                                    clip_sample=False, set_alpha_to_one=False, steps_offset=1)
+        self.scheduler = scheduler or sd_scheduler("ddim")
         self.device = unet.device
 
     @torch.no_grad()
@@ -190,12 +190,16 @@ class StableDiffusionLatentPipeline:
         x = ops.nchw_to_nhwc_raw((lat * sch.init_noise_sigma).contiguous())
         ctx = torch.cat([negative_prompt_embeds, prompt_embeds], 0).to(self.device, torch.float32).contiguous()
         t2 = torch.empty(2 * B, device=self.device, dtype=torch.int64)
-        clip = float(sch.config.clip_sample_range) if sch.config.clip_sample else 0.0
+        plms = isinstance(sch, PNDMScheduler)
+        clip = 0.0 if plms or not sch.config.clip_sample else float(sch.config.clip_sample_range)
         for i, t in enumerate(sch.timesteps.tolist()):
             t2.fill_(t)
             eps = self.unet.forward_nhwc(torch.cat([x, x], 0), t2, ctx)
-            a_t, a_p = sch.step_coefficients(t)
-            ops.cfg_ddim_step_raw(x, eps, guidance_scale, a_t, a_p, clip, out=x)
+            if plms:
+                sch.step_guided(eps, t, x, guidance_scale, out=x)
+            else:
+                a_t, a_p = sch.step_coefficients(t)
+                ops.cfg_ddim_step_raw(x, eps, guidance_scale, a_t, a_p, clip, out=x)
             if callback is not None:
                 callback(i, t, ops.nhwc_to_nchw_raw(x))
         return SimpleNamespace(latents=ops.nhwc_to_nchw_raw(x))

@@ -70,6 +70,7 @@ def parse_args(argv=None, description="Run simple baselines for data attribution
         p.add_argument("--unet_weights", type=str, default=None, help="local state_dict of the base U-Net (optional)")
         p.add_argument("--num_inference_steps", type=int, default=100)
         p.add_argument("--guidance_scale", type=float, default=7.5)
+        p.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "pndm"], help="ddim (default) or pndm: the PLMS sampler SD-1.x repositories ship, num_inference_steps + 1 U-Net calls")
     else:
         p.add_argument("--resolution", type=int, default=256, help="side of the stand-in latent cache's images")
     p.add_argument("--device", type=str, default="cuda:0")
@@ -166,7 +167,7 @@ def generated_latents(args, backend, device):
     pe = torch.load(args.prompt_embeds, map_location="cpu", weights_only=False) if args.prompt_embeds else None
     cond, uncond, _ = prompt_context(prompt, pe, unet.config.cross_attention_dim, device)
     cond, uncond = cond.to(device).unsqueeze(0), uncond.to(device).unsqueeze(0)
-    pipe = backend.StableDiffusionLatentPipeline(unet)
+    pipe = backend.StableDiffusionLatentPipeline(unet, backend.sd_scheduler(args.sampler))
     gen = torch.Generator(device=device).manual_seed(args.seed)
     return [pipe(cond, uncond, generator=gen, num_inference_steps=args.num_inference_steps, guidance_scale=args.guidance_scale,
                  height=args.resolution, width=args.resolution).latents for _ in range(args.num_images)]

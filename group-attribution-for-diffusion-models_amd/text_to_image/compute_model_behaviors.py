@@ -15,6 +15,9 @@ pair), samples stay latents, and the CLIP / aesthetic scorers are a seeded stand
 scores, quantiles, schema - is the reference's).  SSIM and NRMSE (:336-356, scikit-image's `structural_similarity` /
 `normalized_root_mse` on the two uint8 PIL images) are restated here on uint8 pseudo-images of the latents
 (`latents_to_uint8`: the pipeline's own (x/2+0.5).clamp(0,1)*255 round, with latents/4 in the VAE decoder's place).
+`--sampler pndm` generates with the PLMS sampler that SD-1.x repositories ship instead of DDIM (gad.PNDMScheduler); the simple
+loss then runs on its num_inference_steps + 1 timesteps, the repeated one included, as the reference's `pipeline.scheduler.timesteps`.
+The row's keys are the same for both; tell the runs apart by --exp_name.
 
 Where the published files exist the stand-ins give way (nothing changes while none of these is set):
   GAD_VAE_DECODER_TS=/path/decoder.pt   a TorchScript module mapping latents [B,4,h,w], already divided by the VAE's scaling
@@ -121,6 +124,7 @@ def parse_args(argv=None):
     p.add_argument("--unet_weights", type=str, default=None, help="local state_dict of the base U-Net (optional)")
     p.add_argument("--num_inference_steps", type=int, default=100)
     p.add_argument("--guidance_scale", type=float, default=7.5)
+    p.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "pndm"], help="ddim (default) or pndm: the PLMS sampler SD-1.x repositories ship, num_inference_steps + 1 U-Net calls")
     p.add_argument("--device", type=str, default="cuda:0")
     return p.parse_args(argv)
 
@@ -340,8 +344,8 @@ def main(args, backend=None):
     cond, uncond, prompt_encoder = prompt_context(prompt, pe, ctx_dim, device)
     cond, uncond = cond.to(device).unsqueeze(0), uncond.to(device).unsqueeze(0)
 
-    ref_pipe = backend.StableDiffusionLatentPipeline(ref_unet)
-    pipe = backend.StableDiffusionLatentPipeline(unet)
+    # the reference takes the scheduler its model repository ships (:153-164); each pipeline owns one (PNDM keeps state)
+    ref_pipe, pipe = (backend.StableDiffusionLatentPipeline(u, backend.sd_scheduler(args.sampler)) for u in (ref_unet, unet))
     noise_sched = backend.DDPMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                         num_train_timesteps=1000)
     decoder = make_decoder(device)
@@ -401,7 +405,7 @@ def main(args, backend=None):
         times["clip_prompt_score"].append(time.time() - t0 + t_gen)
         t0 = time.time()                                                        # simple loss (:390-417)
         pipe.scheduler.set_timesteps(args.num_inference_steps)
-        ts = pipe.scheduler.timesteps.to(device)
+        ts = pipe.scheduler.timesteps.to(device)                                # pndm: num_inference_steps + 1 entries, one twice
         lists["simple_loss"].append(backend.sd_simple_loss(unet, noise_sched, ref_lat, cond, ts, n_noises=args.n_noises,
                                                            generator=noise_gen))
         sync()

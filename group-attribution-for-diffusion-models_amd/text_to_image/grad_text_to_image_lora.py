@@ -15,7 +15,8 @@ Deliberate deviations: the frozen VAE / CLIP encoders are hub-fetched and outsid
 `{train_data_dir}/latent_cache.pt` as train_text_to_image_lora.py here does (`--synthetic_cache` writes a seeded stand-in) and
 the prompt arrives as embeddings (`--prompt_embeds`, else the text encoder GAD_SD_TEXT_WEIGHTS + GAD_CLIP_BPE name, gad/text.py,
 else a seeded stand-in); generated and journey latents come from
-gad.StableDiffusionLatentPipeline (DDIM) with a per-step callback; noise is drawn per block of `--train_batch_size` rows as one
+gad.StableDiffusionLatentPipeline (DDIM, or PLMS with `--sampler pndm`: num_inference_steps + 1 callbacks, which the journey
+points index as they come) with a per-step callback; noise is drawn per block of `--train_batch_size` rows as one
 [rows][k] draw from a device generator seeded with `--seed` (the reference: one draw per batch per timestep from the global
 generator); the row index of R is the offset in the flat gradient buffer (gad/trak.py)."""
 import argparse
@@ -68,6 +69,7 @@ def parse_args(argv=None):
                    help="fp16 / bf16: bf16 activations (the reference casts the frozen weights to fp16); no: fp32")
     p.add_argument("--timesteps_per_backward", type=int, default=None, help="timesteps of a row per forward / backward")
     p.add_argument("--num_inference_steps", type=int, default=100, help="the reference generates with 100 steps")
+    p.add_argument("--sampler", type=str, default="ddim", choices=["ddim", "pndm"], help="ddim (default) or pndm: the PLMS sampler SD-1.x repositories ship, num_inference_steps + 1 U-Net calls")
     p.add_argument("--prompt_embeds", type=str, default=None, help=".pt with cond / uncond [77, D] text embeddings")
     p.add_argument("--unet_weights", type=str, default=None, help="local state_dict of the base U-Net (optional)")
     p.add_argument("--unet_overrides", type=str, default=None, help="json dict of UNet2DConditionModel kwargs (tests)")
@@ -169,7 +171,7 @@ def main(args, backend=None):
             timesteps = torch.tensor(list(range(0, 1000, 1000 // args.num_timesteps)))                 # :780
         else:
             cond, uncond = prompt_embeddings(args, unet.config.cross_attention_dim)
-            pipe = backend.StableDiffusionLatentPipeline(unet)
+            pipe = backend.StableDiffusionLatentPipeline(unet, backend.sd_scheduler(args.sampler))
             gen = torch.Generator(device=device).manual_seed(args.generation_seed)                      # :487-488
             step_idx, ts, lats, image_idx = [], [], [], []
             for i in range(args.num_images):

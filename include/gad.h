@@ -623,6 +623,33 @@ int gad_ddpm_step(const float* x, const float* eps, float* x_prev, int32_t B, in
                   float alpha_t, float alpha_prev, float clip, int32_t variance_type, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * One PLMS step of the PNDM sampler (csrc/plms.hip; diffusers PNDMScheduler.step_plms with skip_prk_steps, epsilon
+ * prediction - what the reference's StableDiffusionPipeline runs, text_to_image/compute_model_behaviors.py:311-326).
+ * Every operand is n contiguous floats.  Per element:
+ *   e      = eps_u + guidance (eps_c - eps_u)     (eps_c == NULL: e = eps_u, guidance is not read)
+ *   m      = w0 e + w1 h1 + w2 h2 + w3 h3         (h1 the newest stored prediction; a NULL h_i is not read)
+ *   x_prev = cs xs - cm m                         (xs = x; GAD_PLMS_USE_SAVED: xs = x_saved and x is not read)
+ *   push[i]    = e                                (push != NULL: the history slot that receives this prediction)
+ *   x_saved[i] = x                                (GAD_PLMS_SAVE: the first step remembers its sample for the second)
+ * with, for abar_t = alphas_cumprod[t_from] and abar_p = alphas_cumprod[t_to] (gad.schedulers.plms_coefficients),
+ *   cs = sqrt(abar_p / abar_t),  cm = (abar_p - abar_t) / (abar_t sqrt(1 - abar_p) + sqrt(abar_t (1 - abar_t) abar_p)).
+ * The caller forms cs, cm and the weights in fp64; each is rounded once to fp32 here.  With weights (1, 0, 0, 0) the update
+ * is the DDIM eta = 0 step of gad_ddim_step without clipping.  A lane reads all operands of its float4 before it writes, so
+ * x_prev == x (in place) is allowed and push may be one of h1..h3 (a three-slot ring overwrites the slot it read as h3); the
+ * history terms are a prefix (h2 needs h1, h3 needs h2) and the kernel is instantiated on their number and on guidance, so
+ * an absent operand costs no load: at most 24 B read and 8 B written per element.  No workspace, no atomics, a repeated
+ * launch gives equal bits.  Refused with a named error before any HIP call: a null x, eps_u or x_prev; a null x_saved under
+ * GAD_PLMS_SAVE / GAD_PLMS_USE_SAVED; an unknown saved_mode; a base that is not 16-byte aligned; n < 4 or n % 4 != 0; a gap in
+ * the history terms; a non-zero weight for a null h_i; a coefficient that is not finite (in fp64 or after rounding) or
+ * cs <= 0; a guidance that is not finite; x_prev equal to eps or a history slot; push or x_saved equal to x, x_prev, eps or
+ * each other.
+ * ---------------------------------------------------------------------------- */
+enum gad_plms_saved { GAD_PLMS_SAVED_NONE = 0, GAD_PLMS_SAVE = 1, GAD_PLMS_USE_SAVED = 2 };
+int gad_plms_step(const float* x, const float* eps_u, const float* eps_c, float guidance, const float* h1, const float* h2,
+                  const float* h3, float* push, float* x_saved, int32_t saved_mode, float* x_prev, int64_t n, double cs,
+                  double cm, double w0, double w1, double w2, double w3, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Local model behaviours of the unconditional models (csrc/local.hip; reference
  * unconditional_generation/unlearn.py:871-948, calculate_local_scores.py:303-374).
  * All three are order-deterministic (no atomics): a result depends on its own image / segment and on the
