@@ -7,7 +7,7 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$HERE/../include -I$HERE/csrc -Wno-unused-result"
 mkdir -p "$HERE/build"
 pids=()
-for f in gemm_f32 winograd wino4_fused attention norm elementwise optim optim8 transformer half projector local scorenet influence manifold vit similarity vae text lora ddpm plms; do
+for f in gemm_f32 winograd wino4_fused attention norm elementwise optim optim8 transformer half projector local scorenet influence manifold vit similarity vae text lora ddpm plms latent; do
   src="$HERE/csrc/$f.hip"; obj="$HERE/build/$f.o"
   stale=0
   [ -f "$obj" ] || stale=1
@@ -26,5 +26,5 @@ for f in gemm_f32 winograd wino4_fused attention norm elementwise optim optim8 t
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$HERE"/build/{gemm_f32,winograd,wino4_fused,attention,norm,elementwise,optim,optim8,transformer,half,projector,local,scorenet,influence,manifold,vit,similarity,vae,text,lora,ddpm,plms}.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$HERE"/build/{gemm_f32,winograd,wino4_fused,attention,norm,elementwise,optim,optim8,transformer,half,projector,local,scorenet,influence,manifold,vit,similarity,vae,text,lora,ddpm,plms,latent}.o
 echo "built $OUT"

@@ -21,3 +21,4 @@ from .lora import LoraConfig, get_peft_model, lora_parameters, merge_and_unload 
 from .similarity import cosine_rows, group_aggregate, write_baselines  # noqa: F401,E402
 from .vae import AutoencoderKL, VQModel  # noqa: F401,E402
 from .text import CLIPTextModel, CLIPTokenizer, TextTower  # noqa: F401,E402
+from .latents import MomentSource  # noqa: F401,E402

@@ -129,6 +129,7 @@ class LoraDropoutArgs(C.Structure):
 JL_NORMAL, JL_RADEMACHER = 0, 1
 DDPM_FIXED_SMALL, DDPM_FIXED_LARGE = 0, 1
 PLMS_SAVED_NONE, PLMS_SAVE, PLMS_USE_SAVED = 0, 1, 2
+LATENT_SAMPLE, LATENT_RANDOM_FLIP = 1, 2
 POOL_MAX, POOL_AVG, POOL_AVG_VALID = 0, 1, 2
 GELU_ERF, GELU_QUICK = 0, 1
 SIM_X_F32, SIM_X_U8 = 0, 1
@@ -226,6 +227,9 @@ SIGNATURES = {
     # one PLMS step of the PNDM sampler: guidance, multistep combination, transfer, history push (csrc/plms.hip)
     "gad_plms_step": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64,
                                 _vp]),
+    # x0 rows drawn from cached posterior moments; uint8 NHWC -> fp32 NCHW through a table (csrc/latent.hip)
+    "gad_latent_draw": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _i64, C.c_uint32, _f32, _i32, _vp]),
+    "gad_pixels_to_nchw": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i32, _vp]),
     # local model behaviours (csrc/local.hip)
     "gad_image_metrics_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "gad_image_metrics": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _f64, _f64, _f64, _vp, _i64, _vp]),

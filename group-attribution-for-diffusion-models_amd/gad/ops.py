@@ -1675,6 +1675,52 @@ def ddpm_step_raw(x, eps, seeds, t: int, alpha_t: float, alpha_prev: float, clip
     return out
 
 
+def latent_draw_raw(moments, rows, seed: int, step: int, scale: float, sample=True, random_flip=False, out=None, flipped=None):
+    """The x0 rows of one SD training step in one launch (gad_latent_draw): moments [N, F, 2L, h, w] fp32 (F = 1 plain, 2 plain |
+    flipped; mean | logvar along the channels), rows [B] int64 device -> x0 [B, L, h, w] = scale * (mean + std z) of the slab
+    the row's coin picks (`random_flip`), or scale * mean (`sample=False`).  `flipped` (uint8 [B]) receives the slab index.
+    A row is a function of (seed, rows[b], step) alone."""
+    _req(moments, "latent_draw moments")
+    if moments.dim() != 5 or moments.shape[2] % 2:
+        raise _capi.GadError(f"latent_draw: moments must be [N, F, 2L, h, w], got {tuple(moments.shape)}")
+    N, F, L2, h, w = moments.shape
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.is_contiguous() and rows.dim() == 1):
+        raise _capi.GadError(f"latent_draw: rows must be a contiguous 1-D int64 device tensor, got {rows.dtype} {rows.device} "
+                             f"{tuple(rows.shape)}")
+    B, shape = rows.numel(), (rows.numel(), L2 // 2, h, w)
+    out = torch.empty(shape, dtype=torch.float32, device=moments.device) if out is None else _req(out, "latent_draw out")
+    if tuple(out.shape) != shape:
+        raise _capi.GadError(f"latent_draw: out {tuple(out.shape)} must be {shape}")
+    if flipped is not None and not (flipped.is_cuda and flipped.dtype == torch.uint8 and flipped.is_contiguous()
+                                    and flipped.numel() == B):
+        raise _capi.GadError(f"latent_draw: flipped must be a contiguous uint8 device tensor of {B} entries, got {flipped.dtype} "
+                             f"{flipped.device} {tuple(flipped.shape)}")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    flags = (_capi.LATENT_SAMPLE if sample else 0) | (_capi.LATENT_RANDOM_FLIP if random_flip else 0)
+    check(_capi.load().gad_latent_draw(moments.data_ptr(), N, F, (L2 // 2) * h * w, rows.data_ptr(), B, out.data_ptr(),
+                                       _ptr(flipped), seed - (1 << 64) if seed >> 63 else seed, int(step) & 0xFFFFFFFF,
+                                       float(scale), flags, _stream()), "gad_latent_draw")
+    return out
+
+
+def pixels_to_nchw_raw(pixels, lut, flip=False, out=None):
+    """uint8 [B, H, W, C] device pixels -> fp32 [B, C, H, W] = lut[pixel] (gad_pixels_to_nchw), mirrored along W when `flip`.
+    `lut`: 256 fp32 values on the device (gad.similarity.pixel_lut: ToTensor + Normalize([0.5], [0.5]))."""
+    if not (pixels.is_cuda and pixels.dtype == torch.uint8 and pixels.is_contiguous() and pixels.dim() == 4):
+        raise _capi.GadError(f"pixels_to_nchw: expected a contiguous uint8 [B, H, W, C] device tensor, got {pixels.dtype} "
+                             f"{pixels.device} {tuple(pixels.shape)}")
+    _req(lut, "pixels_to_nchw lut")
+    if lut.numel() != 256:
+        raise _capi.GadError(f"pixels_to_nchw: lut must hold 256 values, got {lut.numel()}")
+    B, H, W, Cn = pixels.shape
+    out = torch.empty((B, Cn, H, W), dtype=torch.float32, device=pixels.device) if out is None else _req(out, "pixels_to_nchw out")
+    if tuple(out.shape) != (B, Cn, H, W):
+        raise _capi.GadError(f"pixels_to_nchw: out {tuple(out.shape)} must be {(B, Cn, H, W)}")
+    check(_capi.load().gad_pixels_to_nchw(pixels.data_ptr(), out.data_ptr(), B, H, W, Cn, lut.data_ptr(), int(bool(flip)),
+                                          _stream()), "gad_pixels_to_nchw")
+    return out
+
+
 def plms_step_raw(x, eps, cs: float, cm: float, weights, history=(), push=None, x_saved=None, saved_mode=_capi.PLMS_SAVED_NONE,
                   guidance=None, out=None):
     """One PLMS step in one launch (gad_plms_step): x fp32, eps the U-Net output - of the doubled batch [uncond ; cond] when

@@ -3,9 +3,11 @@
 The reference writes `{data_dir}/metadata.csv` (columns file_name, caption, artist, style, filename) together with
 `{style}_artists.csv` / `{style}_filenames.csv` (text_to_image/artbench/create_metadata.py:77-95,113-114) and reads
 them back through the HF `imagefolder` loader, filtering on `--cls_key style --cls post_impressionism`
-(train_text_to_image_lora.py:911-934,1011-1024).  Here the pixels never reach the trainer (the frozen VAE / CLIP
-encoders are hub-fetched and off the hot path): the tables are joined with precomputed latents and prompt
-embeddings into the `latent_cache.pt` the MI355X trainer keeps resident in HBM.
+(train_text_to_image_lora.py:911-934,1011-1024).  Here the pixels reach the frozen encoders once:
+text_to_image/encode_dataset.py reads the images in `metadata.csv` row order, encodes them with gad.AutoencoderKL (plain and
+mirrored) and the captions with gad.text, and writes `moment_cache.pt` (the posterior moments the trainer samples from under
+`--latent_source moments`), `latent_cache.pt` (their mode; what every other program reads) and `train_pixels.npy`.  The trainer
+keeps whichever file it reads resident in HBM.  `assemble_latent_cache` joins the tables with latents computed elsewhere.
 """
 import os
 

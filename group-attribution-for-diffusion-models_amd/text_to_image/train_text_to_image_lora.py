@@ -7,12 +7,20 @@ of all 32 attentions (:776-820) or loaded, possibly pruned/ragged, from `lora_di
 (:896-902,1122-1127), the hot loop (:1215-1311), `time.csv` (:1203-1209,1315-1319) and
 `pytorch_lora_weights.safetensors` (:1459).
 
-The frozen VAE encoder and CLIP text encoder of the reference are hub-fetched models outside the hot path: this
-entry point trains from a latent cache `{train_data_dir}/latent_cache.pt`
-(dict: latents [N,4,h,w] already multiplied by vae.config.scaling_factor, text_emb [N or 1,77,768], and one
-list per metadata column, e.g. "artist", "filename", "style") - the analogue of the reference's
-`vqvae_output.pt` cache for CelebA (unconditional_generation/main.py:496-525).  `--synthetic_cache` writes a
-seeded stand-in with ArtBench's shape (5 000 images, 258 artists) when no cache exists.
+The frozen VAE encoder and CLIP text encoder run once, in text_to_image/encode_dataset.py (gad.AutoencoderKL and gad.text on
+the HIP operators), which writes the two files this entry point trains from:
+
+  --latent_source cache (default)   `{train_data_dir}/latent_cache.pt` (dict: latents [N,4,h,w] = latent_dist.mode() already
+      multiplied by vae.config.scaling_factor, text_emb [N or 1,77,768], and one list per metadata column, e.g. "artist",
+      "filename", "style") - the analogue of the reference's `vqvae_output.pt` cache for CelebA
+      (unconditional_generation/main.py:496-525): one fixed latent per image.  `--center_crop` and `--random_flip` are
+      accepted and change nothing here.  `--synthetic_cache` writes a seeded stand-in with ArtBench's shape (5 000 images,
+      258 artists) when no cache exists.
+  --latent_source moments           `{train_data_dir}/moment_cache.pt` (gad/latents.py): the posterior moments of every image,
+      plain and mirrored, resident in HBM.  Every step draws `latent_dist.sample() * scaling_factor` afresh, of the mirrored
+      image where `--random_flip`'s coin says so, in one launch (gad_latent_draw): the reference's per-step transform
+      (:1065-1077, 1220-1223) under `--center_crop`, without an encode per step.  Flip and noise are functions of
+      (--seed or 0, image, step) where the reference draws them from unseeded global generators.
 """
 import argparse
 import math
@@ -41,6 +49,12 @@ def parse_args(argv=None):
     p.add_argument("--output_dir", type=str, default="sd-model-finetuned-lora")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--resolution", type=int, default=256)
+    p.add_argument("--center_crop", action="store_true", help="reference :1068; the caches are written under it (encode_dataset.py)")
+    p.add_argument("--random_flip", action="store_true",
+                   help="reference :1069; with --latent_source moments a per-(seed, image, step) coin picks the flipped encode")
+    p.add_argument("--latent_source", type=str, default="cache", choices=["cache", "moments"],
+                   help="cache: one fixed latent per image (latent_cache.pt); moments: a fresh posterior sample per step from "
+                        "moment_cache.pt (gad_latent_draw)")
     p.add_argument("--train_batch_size", type=int, default=16)
     p.add_argument("--num_train_epochs", type=int, default=100)
     p.add_argument("--max_train_steps", type=int, default=None)
@@ -150,6 +164,35 @@ def coalition_rows(a, model_outdir, units_df):
     return np.asarray(rem), np.asarray(rmv)
 
 
+def training_rows(a, cache, n_rows, model_outdir):
+    """Rows of the cache this run trains on: the `--cls_key/--cls` filter, then the coalition over the removal-unit table
+    (:935-1024).  `cache` is either file's dict: latent_cache.pt and moment_cache.pt carry the same metadata columns."""
+    keep = np.arange(n_rows)
+    if a.cls is not None and a.cls_key is not None:
+        keep = keep[np.array(cache[a.cls_key]) == a.cls]
+    if a.removal_dist is not None or a.removal_rank_file is not None:
+        unit_file = os.path.join(a.train_data_dir, f"{a.cls}_{a.removal_unit}s.csv" if a.cls else f"{a.removal_unit}s.csv")
+        units_df = pd.read_csv(unit_file)
+        rem, _ = coalition_rows(a, model_outdir, units_df)
+        kept_units = set(units_df.iloc[rem, 0].tolist())
+        col = np.array(cache[a.removal_unit])[keep]
+        keep = keep[np.isin(col, list(kept_units))]
+        assert set(np.array(cache[a.removal_unit])[keep]) == kept_units or len(keep) == 0
+    return keep
+
+
+def load_moments(a):
+    """`--latent_source moments`: moment_cache.pt, checked against the flags before anything reaches the device"""
+    from gad.latents import MOMENT_CACHE, load_moment_cache
+    path = os.path.join(a.train_data_dir, MOMENT_CACHE)
+    cache = load_moment_cache(path)
+    if a.random_flip and not cache["flips"]:
+        raise ValueError(f"--random_flip: {path} was written with --no_flip and holds no flipped encodes")
+    if cache["resolution"] != a.resolution:
+        raise ValueError(f"--resolution {a.resolution}: {path} was encoded at resolution {cache['resolution']}")
+    return cache
+
+
 def main(a, backend=None):
     if backend is None:
         import gad as backend
@@ -182,24 +225,20 @@ def main(a, backend=None):
         backend.seed_everything(a.seed)
     device = torch.device(a.device)
 
-    # ---- data: latent cache + removal-unit table ----
-    cache_path = os.path.join(a.train_data_dir, "latent_cache.pt")
-    if not os.path.exists(cache_path):
-        if not a.synthetic_cache:
-            raise FileNotFoundError(f"{cache_path} not found (pass --synthetic_cache for a seeded stand-in)")
-        synthetic_cache(cache_path, res=a.resolution)
-    cache = torch.load(cache_path, map_location="cpu", weights_only=False)
-    keep = np.arange(len(cache["latents"]))
-    if a.cls is not None and a.cls_key is not None:
-        keep = keep[np.array(cache[a.cls_key]) == a.cls]
-    if a.removal_dist is not None or a.removal_rank_file is not None:
-        unit_file = os.path.join(a.train_data_dir, f"{a.cls}_{a.removal_unit}s.csv" if a.cls else f"{a.removal_unit}s.csv")
-        units_df = pd.read_csv(unit_file)
-        rem, _ = coalition_rows(a, model_outdir, units_df)
-        kept_units = set(units_df.iloc[rem, 0].tolist())
-        col = np.array(cache[a.removal_unit])[keep]
-        keep = keep[np.isin(col, list(kept_units))]
-        assert set(np.array(cache[a.removal_unit])[keep]) == kept_units or len(keep) == 0
+    # ---- data: latent cache (or posterior moments) + removal-unit table ----
+    if a.latent_source == "moments":
+        cache = load_moments(a)
+        n_rows = len(cache["moments"])
+    else:
+        cache_path = os.path.join(a.train_data_dir, "latent_cache.pt")
+        if not os.path.exists(cache_path):
+            if not a.synthetic_cache:
+                raise FileNotFoundError(f"{cache_path} not found (pass --synthetic_cache for a seeded stand-in, or write it from "
+                                        f"the image folder with text_to_image/encode_dataset.py)")
+            synthetic_cache(cache_path, res=a.resolution)
+        cache = torch.load(cache_path, map_location="cpu", weights_only=False)
+        n_rows = len(cache["latents"])
+    keep = training_rows(a, cache, n_rows, model_outdir)
 
     # ---- model ----
     import json
@@ -223,8 +262,17 @@ def main(a, backend=None):
         unet.save_attn_procs(model_outdir)
         return True
 
-    latents = cache["latents"][keep].to(device)               # resident in HBM (5 000 x 4x32x32 fp32 = 82 MB)
-    text = cache["text_emb"].to(device)
+    source = None
+    if a.latent_source == "moments":                          # both orientations' moments resident (5 000 x 2 x 8x32x32 fp32 = 0.33 GB)
+        from gad.latents import MomentSource
+        source = MomentSource(cache["moments"].to(device), cache["scaling_factor"], a.seed if a.seed is not None else 0)
+        keep_dev = source.subset(keep)
+        text = cache["text_emb"].to(device)
+        if text.shape[0] != 1:
+            text = text.index_select(0, keep_dev)
+    else:
+        latents = cache["latents"][keep].to(device)           # resident in HBM (5 000 x 4x32x32 fp32 = 82 MB)
+        text = cache["text_emb"].to(device)
     steps_per_epoch = math.ceil(len(keep) / a.train_batch_size)
     max_steps = a.max_train_steps or a.num_train_epochs * steps_per_epoch
     sched = backend.DDPMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", num_train_timesteps=1000)
@@ -249,7 +297,10 @@ def main(a, backend=None):
         for s in range(0, len(keep), a.train_batch_size):
             t0 = time.time()
             sel = perm[s:s + a.train_batch_size]
-            x0 = latents.index_select(0, sel)
+            if source is not None:                  # a fresh posterior sample (and flip) per step, as the reference draws (:1220-1223)
+                x0 = source.draw(keep_dev[sel], step, sample=True, random_flip=a.random_flip)
+            else:
+                x0 = latents.index_select(0, sel)
             noise = torch.randn_like(x0)
             if a.noise_offset:                                                          # :1227-1232
                 noise += a.noise_offset * torch.randn((x0.shape[0], x0.shape[1], 1, 1), device=device)

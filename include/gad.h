@@ -650,6 +650,42 @@ int gad_plms_step(const float* x, const float* eps_u, const float* eps_c, float 
                   double cm, double w0, double w1, double w2, double w3, void* stream);
 
 /* ------------------------------------------------------------------------------
+ * The x0 rows of one Stable-Diffusion training step drawn from cached VAE posterior moments (csrc/latent.hip; reference
+ * text_to_image/train_text_to_image_lora.py:1065-1077 RandomHorizontalFlip, :1220-1223
+ * vae.encode(x).latent_dist.sample() * scaling_factor).  The posterior of an image is a function of (image, mirrored or
+ * not), so both are encoded once and kept:
+ *   moments : fp32 [N][F][2][n]   F = 1 (plain encode) or 2 (plain | encode of the mirrored image); per slab mean[n], logvar[n]
+ *   rows    : int64 [B], device   the dataset row of every batch row, clamped to [0, N) in the kernel
+ *   x0      : fp32 [B][n]         flipped : uint8 [B] or NULL - which slab row b was read from
+ * For batch row b with r = rows[b] and element e, with Philox-4x32-10 (Random123 constants), key (seed low 32 bits, high 32 bits):
+ *   coin = bit 0 of word 0 of the block with counter (0xFFFFFFFF, r, step, 3)
+ *   f    = coin if GAD_LATENT_RANDOM_FLIP is set (needs F == 2), else 0;   m, lv = mean, logvar of slab (r, f) at e
+ *   x0   = scale * m                                             flags without GAD_LATENT_SAMPLE: latent_dist.mode(); Philox is
+ *                                                                not called for noise and logvar is not read
+ *   x0   = scale * (m + expf(0.5f * clamp(lv, -30, 20)) * z)     GAD_LATENT_SAMPLE: z is word e & 3 of the block with
+ *                                                                counter (e >> 2, r, step, 3)
+ * through the projector's maps: words x -> u = fl32(fl32(x) * 2^-32 + 2^-33), Box-Muller on (u0,u1), (u2,u3) in the order
+ * r01 cos, r01 sin, r23 cos, r23 sin.  Counter word 3 is this kernel's tag (gad_jl_project uses 0 and 1, gad_ddpm_step 2).
+ * A row's result is a function of (seed, r, step) and the moments alone: it does not depend on B, on the row's position or on
+ * the launch grid, a row repeated in `rows` gives equal rows, and a repeated launch gives equal bits.  12 B of traffic per
+ * element, no workspace, no atomics.  Refused with a named error before any HIP call: a null moments, rows or x0; a base that
+ * is not 16-byte aligned (rows: 8-byte); n % 4 != 0; n / 4 >= 2^32 - 1 (the coin's block index must not be reachable);
+ * N < 1 or N >= 2^32; F outside {1, 2}; GAD_LATENT_RANDOM_FLIP with F == 1; an unknown flag; B < 1.
+ * ---------------------------------------------------------------------------- */
+enum gad_latent_flags { GAD_LATENT_SAMPLE = 1, GAD_LATENT_RANDOM_FLIP = 2 };
+int gad_latent_draw(const float* moments, int64_t N, int32_t F, int64_t n, const int64_t* rows, int32_t B, float* x0,
+                    uint8_t* flipped, int64_t seed, uint32_t step, float scale, int32_t flags, void* stream);
+
+/* uint8 [B][H][W][C] -> fp32 [B][C][H][W] through a 256-entry device table: dst[b][c][h][w] = lut[src[b][h][w'][c]] with
+ * w' = W - 1 - w when flip == 1, else w.  The caller fills the table as gad_cosine_rows' callers fill theirs, in the two fp32
+ * steps u / 255 and (x - 0.5) / 0.5 (ToTensor + Normalize([0.5], [0.5])): the images stay on the device as bytes and the
+ * encoder is fed both orientations without a host round trip.  Any B, H, W, C >= 1; a lane writes one float4 of four
+ * consecutive w when W % 4 == 0 and one float otherwise.  dst 16-byte aligned, lut 4-byte; null pointers, flip outside
+ * {0, 1} and sizes whose product overflows are refused by name before any HIP call. */
+int gad_pixels_to_nchw(const uint8_t* src, float* dst, int64_t B, int32_t H, int32_t W, int32_t C, const float* lut,
+                       int32_t flip, void* stream);
+
+/* ------------------------------------------------------------------------------
  * Local model behaviours of the unconditional models (csrc/local.hip; reference
  * unconditional_generation/unlearn.py:871-948, calculate_local_scores.py:303-374).
  * All three are order-deterministic (no atomics): a result depends on its own image / segment and on the
