@@ -6,9 +6,13 @@ OUT="$HERE/gad/libgad_hip.so"
 HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$HERE/../include -I$HERE/csrc -Wno-unused-result"
 mkdir -p "$HERE/build"
+# the translation units: the compile loop and the link line both read this list
+UNITS="gemm_f32 winograd wino4_fused attention norm elementwise optim optim8 transformer half projector local scorenet influence manifold vit similarity vae text lora sampler latent"
 pids=()
-for f in gemm_f32 winograd wino4_fused attention norm elementwise optim optim8 transformer half projector local scorenet influence manifold vit similarity vae text lora ddpm plms latent; do
+objs=()
+for f in $UNITS; do
   src="$HERE/csrc/$f.hip"; obj="$HERE/build/$f.o"
+  objs+=("$obj")
   stale=0
   [ -f "$obj" ] || stale=1
   for dep in "$src" "$HERE"/csrc/*.h "$HERE/../include/gad.h"; do   # every header: a new one cannot be forgotten
@@ -26,5 +30,5 @@ for f in gemm_f32 winograd wino4_fused attention norm elementwise optim optim8 t
   fi
 done
 for p in "${pids[@]}"; do wait $p; done
-$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "$HERE"/build/{gemm_f32,winograd,wino4_fused,attention,norm,elementwise,optim,optim8,transformer,half,projector,local,scorenet,influence,manifold,vit,similarity,vae,text,lora,ddpm,plms,latent}.o
+$HIPCC --offload-arch=gfx950 -shared -fPIC -o "$OUT" "${objs[@]}"
 echo "built $OUT"

@@ -21,10 +21,7 @@ extern "C" int gad_version(void) { return 100; }
 namespace {
 
 constexpr int NT = 256;
-inline dim3 ew_grid(int64_t n_vec) {
-  int64_t b = gad_ceil_div(n_vec > 0 ? n_vec : 1, NT);
-  return dim3((unsigned)(b < 2048 ? b : 2048));
-}
+inline dim3 ew_grid(int64_t n_vec) { return dim3(gad_stream_grid(n_vec > 0 ? n_vec : 1)); }
 
 // Generic elementwise launcher: F(i4 index, vectors) over n elements; requires 16-B aligned
 // pointers, handles n % 4 tail with the scalar functor.
@@ -56,47 +53,6 @@ __global__ void silu_bwd_kernel(const float* __restrict__ x, const float* __rest
     reinterpret_cast<f32x4*>(dx)[i] = v;
   }
   EW_LOOP_TAIL(n) dx[i] = silu_grad(x[i], dy[i]);
-}
-
-// x / xp are NOT restrict-qualified: the samplers launch this in place (xp == x)
-__global__ void ddim_step_kernel(const float* x, const float* __restrict__ eps, float* xp,
-                                 long n, float sa, float sb, float spa, float spb, float clip) {
-  EW_LOOP_VEC(n) {
-    f32x4 v = reinterpret_cast<const f32x4*>(x)[i], e4 = reinterpret_cast<const f32x4*>(eps)[i], o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float x0 = (v[e] - sb * e4[e]) / sa;
-      if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-      o[e] = spa * x0 + spb * e4[e];
-    }
-    reinterpret_cast<f32x4*>(xp)[i] = o;
-  }
-  EW_LOOP_TAIL(n) {
-    float x0 = (x[i] - sb * eps[i]) / sa;
-    if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-    xp[i] = spa * x0 + spb * eps[i];
-  }
-}
-
-__global__ void cfg_ddim_step_kernel(const float* x, const float* __restrict__ eu, const float* __restrict__ ec,
-                                     float* xp, long n, float gd, float sa, float sb, float spa, float spb, float clip) {
-  EW_LOOP_VEC(n) {
-    f32x4 v = reinterpret_cast<const f32x4*>(x)[i], u = reinterpret_cast<const f32x4*>(eu)[i], c = reinterpret_cast<const f32x4*>(ec)[i], o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float eps = u[e] + gd * (c[e] - u[e]);
-      float x0 = (v[e] - sb * eps) / sa;
-      if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-      o[e] = spa * x0 + spb * eps;
-    }
-    reinterpret_cast<f32x4*>(xp)[i] = o;
-  }
-  EW_LOOP_TAIL(n) {
-    float eps = eu[i] + gd * (ec[i] - eu[i]);
-    float x0 = (x[i] - sb * eps) / sa;
-    if (clip > 0.f) x0 = fminf(fmaxf(x0, -clip), clip);
-    xp[i] = spa * x0 + spb * eps;
-  }
 }
 
 __global__ void to_image01_kernel(const float* __restrict__ x, float* __restrict__ y, long n) {
@@ -321,25 +277,6 @@ extern "C" int gad_silu_bwd(const float* x, const float* dy, float* dx, int64_t 
   GAD_CHECK(x && dy && dx && gad_aligned16(x) && gad_aligned16(dy) && gad_aligned16(dx), "gad_silu_bwd: bad args");
   hipLaunchKernelGGL(silu_bwd_kernel, ew_grid(n / 4), dim3(NT), 0, ST, x, dy, dx, (long)n);
   GAD_LAUNCH_CHECK("gad_silu_bwd");
-  return 0;
-}
-extern "C" int gad_ddim_step(const float* x, const float* eps, float* x_prev, int64_t n, float alpha_t, float alpha_prev,
-                             float clip, void* stream) {
-  GAD_CHECK(x && eps && x_prev && gad_aligned16(x) && gad_aligned16(eps) && gad_aligned16(x_prev), "gad_ddim_step: bad args");
-  GAD_CHECK(alpha_t > 0.f && alpha_t <= 1.f && alpha_prev > 0.f && alpha_prev <= 1.f, "gad_ddim_step: alphas out of (0,1]");
-  float sa = sqrtf(alpha_t), sb = sqrtf(1.f - alpha_t), spa = sqrtf(alpha_prev), spb = sqrtf(1.f - alpha_prev);
-  hipLaunchKernelGGL(ddim_step_kernel, ew_grid(n / 4), dim3(NT), 0, ST, x, eps, x_prev, (long)n, sa, sb, spa, spb, clip);
-  GAD_LAUNCH_CHECK("gad_ddim_step");
-  return 0;
-}
-extern "C" int gad_cfg_ddim_step(const float* x, const float* eps_uc, float* x_prev, int64_t n, float guidance, float alpha_t,
-                                 float alpha_prev, float clip, void* stream) {
-  GAD_CHECK(x && eps_uc && x_prev && n > 0 && n % 4 == 0 && gad_aligned16(x) && gad_aligned16(eps_uc) && gad_aligned16(x_prev),
-            "gad_cfg_ddim_step: bad args (n must be a multiple of 4)");
-  GAD_CHECK(alpha_t > 0.f && alpha_t <= 1.f && alpha_prev > 0.f && alpha_prev <= 1.f, "gad_cfg_ddim_step: alphas out of (0,1]");
-  hipLaunchKernelGGL(cfg_ddim_step_kernel, ew_grid(n / 4), dim3(NT), 0, ST, x, eps_uc, eps_uc + n, x_prev, (long)n, guidance,
-                     sqrtf(alpha_t), sqrtf(1.f - alpha_t), sqrtf(alpha_prev), sqrtf(1.f - alpha_prev), clip);
-  GAD_LAUNCH_CHECK("gad_cfg_ddim_step");
   return 0;
 }
 extern "C" int gad_to_image01(const float* x, float* y, int64_t n, void* stream) {

@@ -32,6 +32,19 @@ void gad_set_error(const char* fmt, ...);
 static inline bool gad_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int64_t gad_ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Grid of a streaming (grid-stride, HBM-bound) kernel: one workgroup per `per_block` items up to 2048 workgroups - 256 CUs x 8
+// resident workgroups of 256 threads - and the loop strides over the rest.  n_items >= 1.
+constexpr int GAD_STREAM_MAX_BLOCKS = 2048;
+static inline unsigned gad_stream_grid(int64_t n_items, int per_block = 256) {
+  const int64_t b = gad_ceil_div(n_items, per_block);
+  return (unsigned)(b < GAD_STREAM_MAX_BLOCKS ? b : GAD_STREAM_MAX_BLOCKS);
+}
+// rows x chunks form: x covers one row's n_items as above, y as many of the rows as keep the whole grid inside the same bound
+static inline dim3 gad_stream_grid_rows(int64_t rows, int64_t n_items) {
+  const int64_t gx = gad_stream_grid(n_items), fit = GAD_STREAM_MAX_BLOCKS / gx;
+  return dim3((unsigned)gx, (unsigned)(rows < fit ? rows : fit));
+}
+
 // wave64 sum reduction (all lanes get the total)
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

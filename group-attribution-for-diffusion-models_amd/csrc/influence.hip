@@ -14,13 +14,12 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAX_BLOCKS = 2048;
+constexpr int MAX_BLOCKS = GAD_STREAM_MAX_BLOCKS;     // the final pass stages a pair per workgroup in LDS
 
-// the one sizing rule: the workspace query and the launch both read it (<= 2048 workgroups of 256, a float4 per lane)
+// the one sizing rule: the workspace query and the launch both read it (the streaming grid, a float4 per lane)
 inline int wf_blocks(int64_t n) {
-  int64_t nv = n / 4;
-  int64_t b = gad_ceil_div(nv > 0 ? nv : 1, NT);
-  return (int)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
+  const int64_t nv = n / 4;
+  return (int)gad_stream_grid(nv > 0 ? nv : 1);
 }
 
 __global__ __launch_bounds__(NT) void wf_dots_part_kernel(const float* __restrict__ o, const float* __restrict__ k,

@@ -16,8 +16,7 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAX_BLOCKS = 2048;     // 8 workgroups per CU, as the other streaming kernels
-constexpr uint32_t TAG = 3u;         // the projector uses 0 and 1, ddpm.hip 2
+constexpr uint32_t TAG = 3u;         // the projector uses 0 and 1, the DDPM step (sampler.hip) 2
 constexpr uint32_t COIN_BLOCK = 0xFFFFFFFFu;
 
 template <bool SAMPLE, bool FLIP>
@@ -104,9 +103,7 @@ extern "C" int gad_latent_draw(const float* moments, int64_t N, int32_t F, int64
             "gad_latent_draw: GAD_LATENT_RANDOM_FLIP needs the flipped slab (F=%d, expected 2)", F);
 
   const long nv = (long)(n / 4);
-  const int64_t gx = std::min<int64_t>(gad_ceil_div(nv, NT), MAX_BLOCKS);
-  const int64_t gy = std::min<int64_t>(B, std::max<int64_t>(1, MAX_BLOCKS / gx));
-  const dim3 grid((unsigned)gx, (unsigned)gy);
+  const dim3 grid = gad_stream_grid_rows(B, nv);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint32_t k0 = (uint32_t)(uint64_t)seed, k1 = (uint32_t)((uint64_t)seed >> 32);
   const bool sample = flags & GAD_LATENT_SAMPLE, flip = flags & GAD_LATENT_RANDOM_FLIP;
@@ -135,7 +132,7 @@ extern "C" int gad_pixels_to_nchw(const uint8_t* src, float* dst, int64_t B, int
             H, W, C);
   const bool vec = W % 4 == 0;
   const long total = (long)B * C * H * (vec ? W / 4 : W);
-  const unsigned grid = (unsigned)std::min<int64_t>(gad_ceil_div(total, NT), MAX_BLOCKS);
+  const unsigned grid = gad_stream_grid(total);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (vec)
     hipLaunchKernelGGL(pixels_to_nchw_kernel<true>, dim3(grid), dim3(NT), 0, st, src, dst, total, (int)H, (int)W, (int)C, lut, (int)flip);

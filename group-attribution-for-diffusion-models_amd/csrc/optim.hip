@@ -68,9 +68,7 @@ __global__ void ema_kernel(float* __restrict__ ema, const float* __restrict__ p,
 
 extern "C" int gad_ema_update(float* ema, const float* p, int64_t n, float decay, void* stream) {
   GAD_CHECK(ema && p && n > 0 && gad_aligned16(ema) && gad_aligned16(p), "gad_ema_update: bad args");
-  int64_t blocks = gad_ceil_div(n / 4 + 1, 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, 1.f - decay);
+  hipLaunchKernelGGL(ema_kernel, dim3(gad_stream_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, ema, p, (long)n, 1.f - decay);
   GAD_LAUNCH_CHECK("gad_ema_update");
   return 0;
 }
@@ -86,9 +84,7 @@ extern "C" int gad_clip_adam_ema(const gad_adam_args* a, void* stream) {
   d.bc1 = (float)(1.0 - pow((double)a->beta1, (double)a->step));
   d.rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)a->beta2, (double)a->step)));
   d.ema_om = 1.f - a->ema_decay;
-  int64_t blocks = gad_ceil_div(a->n / 4 + 1, 256);
-  if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d);
+  hipLaunchKernelGGL(adam_kernel, dim3(gad_stream_grid(a->n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, d);
   GAD_LAUNCH_CHECK("gad_clip_adam_ema");
   return 0;
 }

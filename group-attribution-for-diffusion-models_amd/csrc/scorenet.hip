@@ -8,7 +8,7 @@
 //   gad_relu             in place on a [rows][C] slice of a [rows][ld] buffer.
 //
 // One thread per output element (float4 of channels on the vector path, else one float): consecutive lanes walk consecutive
-// channels, then pixels, so every wave's loads and stores are contiguous runs.  Grid-stride over at most MAX_BLOCKS
+// channels, then pixels, so every wave's loads and stores are contiguous runs.  Grid-stride over at most GAD_STREAM_MAX_BLOCKS
 // workgroups; every element offset is 64-bit.  Contraction into fma is off: the resize weights its four taps in one stated
 // order.
 #include <math.h>
@@ -20,7 +20,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int64_t MAX_BLOCKS = 2048;      // 256 CUs x 8 workgroups; the rest of the work is grid-strided
 
 template <int V> struct Vec;
 template <> struct Vec<1> { typedef float T; };
@@ -145,8 +144,6 @@ __global__ __launch_bounds__(NT) void relu_kernel(float* __restrict__ x, int64_t
   }
 }
 
-unsigned grid_of(int64_t total) { return (unsigned)(gad_ceil_div(total, NT) < MAX_BLOCKS ? gad_ceil_div(total, NT) : MAX_BLOCKS); }
-
 const double TOO_LARGE = 4e18;            // element counts stay inside int64
 
 }  // namespace
@@ -175,8 +172,8 @@ extern "C" int gad_pool2d(const float* x, float* y, int32_t B, int32_t H, int32_
   g.cv = v4 ? C / 4 : C;
   g.ldx = ldx, g.ldy = ldy;
   g.total = (int64_t)B * Ho * Wo * g.cv;
-  if (v4) hipLaunchKernelGGL(pool2d_kernel<4>, dim3(grid_of(g.total)), dim3(NT), 0, ST, x, y, g);
-  else hipLaunchKernelGGL(pool2d_kernel<1>, dim3(grid_of(g.total)), dim3(NT), 0, ST, x, y, g);
+  if (v4) hipLaunchKernelGGL(pool2d_kernel<4>, dim3(gad_stream_grid(g.total)), dim3(NT), 0, ST, x, y, g);
+  else hipLaunchKernelGGL(pool2d_kernel<1>, dim3(gad_stream_grid(g.total)), dim3(NT), 0, ST, x, y, g);
   GAD_LAUNCH_CHECK("gad_pool2d");
   return 0;
 }
@@ -193,8 +190,8 @@ extern "C" int gad_resize_bilinear(const float* x, float* y, int32_t B, int32_t 
   g.cv = v4 ? C / 4 : C;
   g.sh = (double)H / (double)Ho, g.sw = (double)W / (double)Wo;
   g.total = (int64_t)B * Ho * Wo * g.cv;
-  if (v4) hipLaunchKernelGGL(resize_bilinear_kernel<4>, dim3(grid_of(g.total)), dim3(NT), 0, ST, x, y, g);
-  else hipLaunchKernelGGL(resize_bilinear_kernel<1>, dim3(grid_of(g.total)), dim3(NT), 0, ST, x, y, g);
+  if (v4) hipLaunchKernelGGL(resize_bilinear_kernel<4>, dim3(gad_stream_grid(g.total)), dim3(NT), 0, ST, x, y, g);
+  else hipLaunchKernelGGL(resize_bilinear_kernel<1>, dim3(gad_stream_grid(g.total)), dim3(NT), 0, ST, x, y, g);
   GAD_LAUNCH_CHECK("gad_resize_bilinear");
   return 0;
 }
@@ -207,8 +204,8 @@ extern "C" int gad_relu(float* x, int64_t rows, int32_t C, int32_t ld, void* str
   const bool v4 = C % 4 == 0 && ld % 4 == 0 && gad_aligned16(x);
   const int cv = v4 ? C / 4 : C;
   const int64_t total = rows * cv;
-  if (v4) hipLaunchKernelGGL(relu_kernel<4>, dim3(grid_of(total)), dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
-  else hipLaunchKernelGGL(relu_kernel<1>, dim3(grid_of(total)), dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
+  if (v4) hipLaunchKernelGGL(relu_kernel<4>, dim3(gad_stream_grid(total)), dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
+  else hipLaunchKernelGGL(relu_kernel<1>, dim3(gad_stream_grid(total)), dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
   GAD_LAUNCH_CHECK("gad_relu");
   return 0;
 }

@@ -195,17 +195,13 @@ extern "C" int gad_layernorm_bwd(const float* x, const float* dy, float* dx, con
 
 extern "C" int gad_geglu_fwd(const float* h, float* out, int64_t M, int32_t F, void* stream) {
   GAD_CHECK(h && out && M > 0 && F > 0 && F % 4 == 0 && gad_aligned16(h) && gad_aligned16(out), "gad_geglu_fwd: needs F%%4==0 and 16-B alignment");
-  long nv = M * (F / 4);
-  long b = gad_ceil_div(nv, 256);
-  hipLaunchKernelGGL(geglu_fwd_kernel, dim3((unsigned)(b < 2048 ? b : 2048)), dim3(256), 0, (hipStream_t)stream, h, out, (long)M, F / 4);
+  hipLaunchKernelGGL(geglu_fwd_kernel, dim3(gad_stream_grid(M * (F / 4))), dim3(256), 0, (hipStream_t)stream, h, out, (long)M, F / 4);
   GAD_LAUNCH_CHECK("gad_geglu_fwd");
   return 0;
 }
 extern "C" int gad_geglu_bwd(const float* h, const float* dout, float* dh, int64_t M, int32_t F, void* stream) {
   GAD_CHECK(h && dout && dh && M > 0 && F > 0 && F % 4 == 0 && gad_aligned16(h) && gad_aligned16(dout) && gad_aligned16(dh), "gad_geglu_bwd: needs F%%4==0 and 16-B alignment");
-  long nv = M * (F / 4);
-  long b = gad_ceil_div(nv, 256);
-  hipLaunchKernelGGL(geglu_bwd_kernel, dim3((unsigned)(b < 2048 ? b : 2048)), dim3(256), 0, (hipStream_t)stream, h, dout, dh, (long)M, F / 4);
+  hipLaunchKernelGGL(geglu_bwd_kernel, dim3(gad_stream_grid(M * (F / 4))), dim3(256), 0, (hipStream_t)stream, h, dout, dh, (long)M, F / 4);
   GAD_LAUNCH_CHECK("gad_geglu_bwd");
   return 0;
 }

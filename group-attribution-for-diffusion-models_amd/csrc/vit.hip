@@ -20,7 +20,6 @@
 namespace {
 
 constexpr int NT = 256, WPB = NT / 64;
-constexpr int64_t MAX_BLOCKS = 2048;      // 256 CUs x 8 workgroups; the rest of the work is grid-strided
 constexpr int MAX_LDS = 64 * 1024;
 const double TOO_LARGE = 4e18;            // element counts stay inside int64
 
@@ -238,11 +237,6 @@ __global__ __launch_bounds__(NT) void l2_normalize_kernel(float* __restrict__ x,
   }
 }
 
-unsigned grid_of(int64_t units, int per_block) {
-  const int64_t nb = gad_ceil_div(units, per_block);
-  return (unsigned)(nb < MAX_BLOCKS ? nb : MAX_BLOCKS);
-}
-
 // the geometry checks shared by the workspace query and the launch -> nullptr or a message
 const char* resize_refusal(int32_t H, int32_t W, int32_t rh, int32_t rw, int32_t oy, int32_t ox, int32_t R, int32_t P) {
   if (H < 1 || W < 1 || rh < 1 || rw < 1 || R < 1 || P < 1) return "H, W, rh, rw, R and P must all be >= 1";
@@ -325,8 +319,8 @@ extern "C" int gad_vit_tokens(const float* patches, const float* cls, const floa
   const bool v4 = C % 4 == 0 && gad_aligned16(patches) && gad_aligned16(cls) && gad_aligned16(pos) && gad_aligned16(out) &&
                   (gamma == nullptr || (gad_aligned16(gamma) && gad_aligned16(beta)));
   const int64_t rows = (int64_t)B * T;
-  if (v4) hipLaunchKernelGGL(vit_tokens_kernel<4>, dim3(grid_of(rows, WPB)), dim3(NT), 0, ST, patches, cls, pos, gamma, beta, out, rows, T, C, eps);
-  else hipLaunchKernelGGL(vit_tokens_kernel<1>, dim3(grid_of(rows, WPB)), dim3(NT), 0, ST, patches, cls, pos, gamma, beta, out, rows, T, C, eps);
+  if (v4) hipLaunchKernelGGL(vit_tokens_kernel<4>, dim3(gad_stream_grid(rows, WPB)), dim3(NT), 0, ST, patches, cls, pos, gamma, beta, out, rows, T, C, eps);
+  else hipLaunchKernelGGL(vit_tokens_kernel<1>, dim3(gad_stream_grid(rows, WPB)), dim3(NT), 0, ST, patches, cls, pos, gamma, beta, out, rows, T, C, eps);
   GAD_LAUNCH_CHECK("gad_vit_tokens");
   return 0;
 }
@@ -340,7 +334,7 @@ extern "C" int gad_gelu(float* x, int64_t rows, int32_t C, int32_t ld, int32_t k
   const bool v4 = C % 4 == 0 && ld % 4 == 0 && gad_aligned16(x);
   const int cv = v4 ? C / 4 : C;
   const int64_t total = rows * cv;
-  const dim3 grid(grid_of(total, NT));
+  const dim3 grid(gad_stream_grid(total, NT));
   if (v4 && kind == GAD_GELU_ERF) hipLaunchKernelGGL((gelu_kernel<4, 0>), grid, dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
   else if (v4) hipLaunchKernelGGL((gelu_kernel<4, 1>), grid, dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
   else if (kind == GAD_GELU_ERF) hipLaunchKernelGGL((gelu_kernel<1, 0>), grid, dim3(NT), 0, ST, x, total, cv, (int64_t)ld);
@@ -355,8 +349,8 @@ extern "C" int gad_l2_normalize_rows(float* x, int64_t rows, int32_t C, int32_t 
   GAD_CHECK(ld >= C, "gad_l2_normalize_rows: ld=%d < C=%d", ld, C);
   GAD_CHECK((double)rows * ld < TOO_LARGE, "gad_l2_normalize_rows: tensor too large");
   const bool v4 = C % 4 == 0 && ld % 4 == 0 && gad_aligned16(x);
-  if (v4) hipLaunchKernelGGL(l2_normalize_kernel<4>, dim3(grid_of(rows, WPB)), dim3(NT), 0, ST, x, rows, C, (int64_t)ld);
-  else hipLaunchKernelGGL(l2_normalize_kernel<1>, dim3(grid_of(rows, WPB)), dim3(NT), 0, ST, x, rows, C, (int64_t)ld);
+  if (v4) hipLaunchKernelGGL(l2_normalize_kernel<4>, dim3(gad_stream_grid(rows, WPB)), dim3(NT), 0, ST, x, rows, C, (int64_t)ld);
+  else hipLaunchKernelGGL(l2_normalize_kernel<1>, dim3(gad_stream_grid(rows, WPB)), dim3(NT), 0, ST, x, rows, C, (int64_t)ld);
   GAD_LAUNCH_CHECK("gad_l2_normalize_rows");
   return 0;
 }

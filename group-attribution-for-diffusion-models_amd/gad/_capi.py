@@ -222,9 +222,9 @@ SIGNATURES = {
     # random projection (csrc/projector.hip)
     "gad_jl_project_workspace_bytes": (_i64, [C.POINTER(JLArgs)]),
     "gad_jl_project": (C.c_int, [C.POINTER(JLArgs), _vp]),
-    # ancestral DDPM update with in-kernel noise (csrc/ddpm.hip)
+    # ancestral DDPM update with in-kernel noise (csrc/sampler.hip)
     "gad_ddpm_step": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _f32, _f32, _f32, _i32, _vp]),
-    # one PLMS step of the PNDM sampler: guidance, multistep combination, transfer, history push (csrc/plms.hip)
+    # one PLMS step of the PNDM sampler: guidance, multistep combination, transfer, history push (csrc/sampler.hip)
     "gad_plms_step": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _f64, _f64, _f64, _f64, _f64, _f64,
                                 _vp]),
     # x0 rows drawn from cached posterior moments; uint8 NHWC -> fp32 NCHW through a table (csrc/latent.hip)

@@ -19,7 +19,7 @@ import torch
 
 from . import ops
 from .nn import UNet2DModel
-from .pipelines import DDPMPipeline
+from .pipelines import DDPMPipeline, ddim_update, denoising_steps
 from .schedulers import DDIMScheduler, DDPMScheduler
 from .training import EMAModel, FusedTrainer
 
@@ -94,16 +94,18 @@ class FusedSampler:
         """The DDIM trajectory alone: yields after every enqueued step, returns x (updated in place) = x_0, NHWC."""
         sch = self.sch
         sch.set_timesteps(num_inference_steps)
-        clip = float(sch.config.clip_sample_range) if sch.config.clip_sample else 0.0
         t = torch.empty(x.shape[0], device=x.device, dtype=torch.int64)
-        for ts in sch.timesteps.tolist():
+        update = ddim_update(sch)
+
+        # no_grad around each step's work, not around the yields: another coalition's training runs between them
+        def step_predict(x, t):
             with torch.no_grad():
-                t.fill_(ts)
-                eps = self.unet.forward_nhwc(x, t)
-                a_t, a_p = sch.step_coefficients(ts)
-                ops.ddim_step_raw(x, eps, a_t, a_p, clip, out=x)
-            yield
-        return x
+                return self.unet.forward_nhwc(x, t)
+
+        def step_update(x, eps, ts):
+            with torch.no_grad():
+                update(x, eps, ts)
+        return (yield from denoising_steps(x, sch.timesteps.tolist(), t, step_predict, step_update))
 
     def denoise_steps(self, x: torch.Tensor, num_inference_steps: int):
         """Generator form of `denoise`: yields after every enqueued DDIM step (the pipelined scheduler interleaves another

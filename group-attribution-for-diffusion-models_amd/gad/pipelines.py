@@ -13,7 +13,28 @@ from types import SimpleNamespace
 import torch
 
 from . import ops
-from .schedulers import DDIMScheduler, PNDMScheduler
+from .schedulers import DDIMScheduler, PNDMScheduler, randn_tensor
+
+
+def denoising_steps(x, timesteps, tdev, predict, update):
+    """The denoising loop of every sampler, as a generator: per host timestep t it fills the device timestep tensor `tdev`,
+    takes eps = predict(x, tdev) and lets update(x, eps, t) write x.  Yields (step index, t) once per enqueued step - the
+    callers' per-step hook (a callback; the coalition scheduler interleaves other work there) - and returns x."""
+    for i, t in enumerate(timesteps):
+        tdev.fill_(t)
+        update(x, predict(x, tdev), t)
+        yield i, t
+    return x
+
+
+def ddim_update(scheduler):
+    """update(x, eps, t) of denoising_steps for a DDIMScheduler: one gad_ddim_step launch, in place."""
+    clip = scheduler.clip
+
+    def update(x, eps, t):
+        a_t, a_p = scheduler.step_coefficients(t)
+        ops.ddim_step_raw(x, eps, a_t, a_p, clip, out=x)
+    return update
 
 
 class DDPMPipeline:
@@ -37,30 +58,24 @@ class DDPMPipeline:
     def _run_steps(self, x, num_inference_steps, generator=None):
         """x: NHWC device tensor, updated in place through all timesteps."""
         sch = self.scheduler
-        if not isinstance(sch, DDIMScheduler):
+        ts = sch.timesteps.tolist()
+        tdev = torch.empty(x.shape[0], device=x.device, dtype=torch.int64)
+        ddim = isinstance(sch, DDIMScheduler)
+        if ddim:
+            update = ddim_update(sch)
+        else:
             # any other scheduler with the diffusers step() protocol (DDPMScheduler: ancestral sampling).  Off the
             # reference's path (its samplers are DDIM); the step sees NCHW views so that its noise draws keep diffusers' order
-            tdev = torch.empty(x.shape[0], device=x.device, dtype=torch.int64)
-            for t in sch.timesteps.tolist():
-                tdev.fill_(t)
-                eps = self.unet.forward_nhwc(x, tdev)
+            def update(x, eps, t):
                 nxt = sch.step(eps.permute(0, 3, 1, 2), t, x.permute(0, 3, 1, 2), generator=generator).prev_sample
                 x.copy_(nxt.permute(0, 2, 3, 1))
-            return x
-        clip = float(sch.config.clip_sample_range) if sch.config.clip_sample else 0.0
-        B = x.shape[0]
-        tdev = torch.empty(B, device=x.device, dtype=torch.int64)
-        use_graph = self.use_graph and isinstance(sch, DDIMScheduler)
-        if not use_graph:
-            for t in sch.timesteps.tolist():
-                tdev.fill_(t)
-                eps = self.unet.forward_nhwc(x, tdev)
-                a_t, a_p = sch.step_coefficients(t)
-                ops.ddim_step_raw(x, eps, a_t, a_p, clip, out=x)
+        if not (self.use_graph and ddim):
+            for _ in denoising_steps(x, ts, tdev, self.unet.forward_nhwc, update):
+                pass
             return x
         # one captured graph per distinct (a_t, a_p) would defeat the purpose: capture the U-Net
         # forward once (t is a device tensor) and launch the tiny DDIM kernel eagerly after it.
-        key = (B, tuple(x.shape[1:]))
+        key = (x.shape[0], tuple(x.shape[1:]))
         g = self._graphs.get(key)
         if g is None:
             g = SimpleNamespace(x=torch.zeros_like(x), t=torch.zeros_like(tdev), eps=None, graph=None)
@@ -75,11 +90,12 @@ class DDPMPipeline:
             self._graphs[key] = g
         g.x.copy_(x)
         ops.refresh_wino(self.unet)            # derived weights the captured launches read at fixed addresses
-        for t in sch.timesteps.tolist():
-            g.t.fill_(t)
+
+        def replay(_x, _t):                    # the capture reads g.x and g.t, the state and timestep tensor of this loop
             g.graph.replay()
-            a_t, a_p = sch.step_coefficients(t)
-            ops.ddim_step_raw(g.x, g.eps, a_t, a_p, clip, out=g.x)
+            return g.eps
+        for _ in denoising_steps(g.x, ts, g.t, replay, update):
+            pass
         x.copy_(g.x)
         return x
 
@@ -91,10 +107,7 @@ class DDPMPipeline:
         cfg = self.unet.config
         ss = cfg.sample_size if isinstance(cfg.sample_size, (tuple, list)) else (cfg.sample_size, cfg.sample_size)
         shape = (batch_size, cfg.in_channels, *ss)
-        if generator is not None and generator.device.type == "cpu":
-            noise = torch.randn(shape, generator=generator, dtype=torch.float32).to(self.device)
-        else:
-            noise = torch.randn(shape, generator=generator, dtype=torch.float32, device=self.device)
+        noise = randn_tensor(shape, generator, self.device)
         self.scheduler.set_timesteps(num_inference_steps)
         x = ops.nchw_to_nhwc_raw(noise.contiguous())
         x = self._run_steps(x, num_inference_steps, generator)
@@ -181,25 +194,24 @@ class StableDiffusionLatentPipeline:
         B = prompt_embeds.shape[0]
         hw = (height or cfg.sample_size * 8) // 8, (width or cfg.sample_size * 8) // 8
         shape = (B, cfg.in_channels, *hw)
-        if generator is not None and generator.device.type == "cpu":
-            lat = torch.randn(shape, generator=generator, dtype=torch.float32).to(self.device)
-        else:
-            lat = torch.randn(shape, generator=generator, dtype=torch.float32, device=self.device)
+        lat = randn_tensor(shape, generator, self.device)
         sch = self.scheduler
         sch.set_timesteps(num_inference_steps)
         x = ops.nchw_to_nhwc_raw((lat * sch.init_noise_sigma).contiguous())
         ctx = torch.cat([negative_prompt_embeds, prompt_embeds], 0).to(self.device, torch.float32).contiguous()
         t2 = torch.empty(2 * B, device=self.device, dtype=torch.int64)
-        plms = isinstance(sch, PNDMScheduler)
-        clip = 0.0 if plms or not sch.config.clip_sample else float(sch.config.clip_sample_range)
-        for i, t in enumerate(sch.timesteps.tolist()):
-            t2.fill_(t)
-            eps = self.unet.forward_nhwc(torch.cat([x, x], 0), t2, ctx)
-            if plms:
+        clip = sch.clip
+
+        def predict(x, t2):
+            return self.unet.forward_nhwc(torch.cat([x, x], 0), t2, ctx)
+
+        def update(x, eps, t):
+            if isinstance(sch, PNDMScheduler):
                 sch.step_guided(eps, t, x, guidance_scale, out=x)
             else:
                 a_t, a_p = sch.step_coefficients(t)
                 ops.cfg_ddim_step_raw(x, eps, guidance_scale, a_t, a_p, clip, out=x)
+        for i, t in denoising_steps(x, sch.timesteps.tolist(), t2, predict, update):
             if callback is not None:
                 callback(i, t, ops.nhwc_to_nchw_raw(x))
         return SimpleNamespace(latents=ops.nhwc_to_nchw_raw(x))
@@ -215,10 +227,7 @@ def sd_simple_loss(unet, scheduler, latents0, prompt_embeds, timesteps, n_noises
     total = 0.0
     with torch.no_grad():
         for _ in range(n_noises):
-            if generator is not None and generator.device.type == "cpu":      # host draw, then moved (randn_tensor semantics)
-                eps = torch.randn(z.shape, generator=generator, dtype=torch.float32).to(dev)
-            else:
-                eps = torch.randn(z.shape, generator=generator, device=dev, dtype=torch.float32)
+            eps = randn_tensor(z.shape, generator, dev)
             noisy = scheduler.add_noise(z, eps, timesteps.to(dev))
             pred = unet(noisy, timesteps.to(dev), ctx).sample
             loss, _ = ops.mse_fwd_bwd_raw(pred.contiguous(), eps)

@@ -23,7 +23,41 @@ def _betas(beta_start, beta_end, n, schedule, trained_betas=None):
     raise NotImplementedError(f"beta_schedule={schedule}")
 
 
+def randn_tensor(shape, generator, device, dtype=torch.float32):
+    """diffusers' randn_tensor: a CPU generator draws on the host and the tensor is moved (the same noise on every device);
+    any other generator, or none, draws on `device`."""
+    if generator is not None and generator.device.type == "cpu":
+        return torch.randn(shape, generator=generator, dtype=dtype).to(device)
+    return torch.randn(shape, generator=generator, dtype=dtype, device=device)
+
+
 class _Base:
+    @property
+    def clip(self):
+        """The x0 clamp of the step kernels: clip_sample_range, or 0.0 (no clamp) without clip_sample (PNDM has none)."""
+        c = self.config
+        return float(c.clip_sample_range) if c.get("clip_sample") else 0.0
+
+    @property
+    def stride(self):
+        """Timesteps between two visited ones, T // n (needs set_timesteps)."""
+        return self.config.num_train_timesteps // self.num_inference_steps
+
+    def alpha_pair(self, t_from, t_to):
+        """(alpha_bar[t_from], alpha_bar[t_to]) as python floats holding the float32 table values; t_to < 0 is past the
+        last step and takes the final alpha: final_alpha_cumprod where the scheduler has one, 1.0 for DDPM."""
+        ac = self.alphas_cumprod
+        final = getattr(self, "final_alpha_cumprod", None)
+        a_to = ac[t_to].item() if t_to >= 0 else 1.0 if final is None else final.item()
+        return ac[t_from].item(), a_to
+
+    def _set_inference_steps(self, num_inference_steps):
+        """Records n and returns the ascending leading-spacing grid k (T // n) + steps_offset, k = 0 .. n - 1 (int64)."""
+        if num_inference_steps > self.config.num_train_timesteps:
+            raise ValueError("num_inference_steps > num_train_timesteps")
+        self.num_inference_steps = num_inference_steps
+        return (np.arange(0, num_inference_steps) * self.stride).round().astype(np.int64) + self.config.steps_offset
+
     def _tables(self, c):
         self.betas = _betas(c["beta_start"], c["beta_end"], c["num_train_timesteps"], c["beta_schedule"],
                             c.get("trained_betas"))
@@ -61,12 +95,7 @@ class DDPMScheduler(_Base):
         self.timesteps = torch.from_numpy(np.arange(0, num_train_timesteps)[::-1].copy())
 
     def set_timesteps(self, num_inference_steps, device=None):
-        if num_inference_steps > self.config.num_train_timesteps:
-            raise ValueError("num_inference_steps > num_train_timesteps")
-        self.num_inference_steps = num_inference_steps
-        ratio = self.config.num_train_timesteps // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64) + self.config.steps_offset
-        self.timesteps = torch.from_numpy(ts)
+        self.timesteps = torch.from_numpy(self._set_inference_steps(num_inference_steps)[::-1].copy())
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True):
         """Ancestral DDPM update (diffusers DDPMScheduler.step, epsilon prediction, variance_type fixed_small / fixed_large):
@@ -77,11 +106,7 @@ class DDPMScheduler(_Base):
         if c.prediction_type != "epsilon" or c.thresholding or c.variance_type not in ("fixed_small", "fixed_large"):
             raise NotImplementedError("DDPMScheduler.step: epsilon prediction with fixed variance only")
         t = int(timestep)
-        n = self.num_inference_steps or c.num_train_timesteps
-        prev_t = t - c.num_train_timesteps // n
-        ac = self.alphas_cumprod
-        a_t = ac[t].item()
-        a_p = ac[prev_t].item() if prev_t >= 0 else 1.0
+        a_t, a_p = self.alpha_pair(t, t - (self.stride if self.num_inference_steps else 1))    # no set_timesteps: all T steps
         cur_alpha = a_t / a_p
         cur_beta = 1.0 - cur_alpha
         x0 = (sample - (1.0 - a_t) ** 0.5 * model_output) / a_t ** 0.5
@@ -90,11 +115,7 @@ class DDPMScheduler(_Base):
         mean = (a_p ** 0.5 * cur_beta / (1.0 - a_t)) * x0 + (cur_alpha ** 0.5 * (1.0 - a_p) / (1.0 - a_t)) * sample
         if t > 0:
             var = max((1.0 - a_p) / (1.0 - a_t) * cur_beta, 1e-20) if c.variance_type == "fixed_small" else cur_beta
-            if generator is not None and generator.device.type == "cpu" and sample.is_cuda:
-                z = torch.randn(sample.shape, generator=generator, dtype=sample.dtype).to(sample.device)
-            else:
-                z = torch.randn(sample.shape, generator=generator, dtype=sample.dtype, device=sample.device)
-            mean = mean + var ** 0.5 * z
+            mean = mean + var ** 0.5 * randn_tensor(sample.shape, generator, sample.device, sample.dtype)
         return SimpleNamespace(prev_sample=mean)
 
 
@@ -127,21 +148,12 @@ class DDIMScheduler(_Base):
         return cls(**dict(config))
 
     def set_timesteps(self, num_inference_steps, device=None):
-        if num_inference_steps > self.config.num_train_timesteps:
-            raise ValueError("num_inference_steps > num_train_timesteps")
-        self.num_inference_steps = num_inference_steps
-        ratio = self.config.num_train_timesteps // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
-        ts += self.config.steps_offset
-        self.timesteps = torch.from_numpy(ts)          # kept on the host: the loop index is host data
+        self.timesteps = torch.from_numpy(self._set_inference_steps(num_inference_steps)[::-1].copy())   # host data: the loop index
 
     def step_coefficients(self, timestep):
         """(alpha_bar_t, alpha_bar_prev) as python floats holding the float32 table values."""
         t = int(timestep)
-        prev = t - self.config.num_train_timesteps // self.num_inference_steps
-        a_t = self.alphas_cumprod[t].item()
-        a_p = self.alphas_cumprod[prev].item() if prev >= 0 else self.final_alpha_cumprod.item()
-        return a_t, a_p
+        return self.alpha_pair(t, t - self.stride)
 
     def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None,
              variance_noise=None, return_dict=True, out=None):
@@ -149,8 +161,7 @@ class DDIMScheduler(_Base):
             raise NotImplementedError("DDIMScheduler.step: the reference samples with eta=0 "
                                       "(src/diffusion_utils.py:336-341)")
         a_t, a_p = self.step_coefficients(timestep)
-        clip = float(self.config.clip_sample_range) if self.config.clip_sample else 0.0
-        prev = ops.ddim_step_raw(sample.contiguous(), model_output.contiguous(), a_t, a_p, clip, out=out)
+        prev = ops.ddim_step_raw(sample.contiguous(), model_output.contiguous(), a_t, a_p, self.clip, out=out)
         return SimpleNamespace(prev_sample=prev)
 
 
@@ -221,11 +232,7 @@ class PNDMScheduler(_Base):
         self._newest = -1                 # ring slot of the newest one
 
     def set_timesteps(self, num_inference_steps, device=None):
-        if num_inference_steps > self.config.num_train_timesteps:
-            raise ValueError("num_inference_steps > num_train_timesteps")
-        self.num_inference_steps = num_inference_steps
-        r = self.config.num_train_timesteps // num_inference_steps
-        ts = (np.arange(0, num_inference_steps) * r).round().astype(np.int64) + self.config.steps_offset
+        ts = self._set_inference_steps(num_inference_steps)
         self.timesteps = torch.from_numpy(np.concatenate([ts[:-1], ts[-2:-1], ts[-1:]])[::-1].copy())   # host data, as DDIM's
         self._reset()
 
@@ -233,11 +240,8 @@ class PNDMScheduler(_Base):
         """(cs, cm, weights, push, use_saved, save) of the step about to be taken at `timestep` (host floats, fp64)."""
         if self.num_inference_steps is None:
             raise ValueError("PNDMScheduler: set_timesteps has not been called")
-        r = self.config.num_train_timesteps // self.num_inference_steps
-        t_from, t_to, w, push, use_saved, save = plms_plan(self.counter, self.n_stored, int(timestep), r)
-        a_t = self.alphas_cumprod[t_from].item()
-        a_p = self.alphas_cumprod[t_to].item() if t_to >= 0 else self.final_alpha_cumprod.item()
-        return (*plms_coefficients(a_t, a_p), w, push, use_saved, save)
+        t_from, t_to, w, push, use_saved, save = plms_plan(self.counter, self.n_stored, int(timestep), self.stride)
+        return (*plms_coefficients(*self.alpha_pair(t_from, t_to)), w, push, use_saved, save)
 
     def _state(self, sample):
         if self._ring is None or self._ring.device != sample.device or self._ring.shape[1] != sample.numel():

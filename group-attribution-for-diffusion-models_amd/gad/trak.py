@@ -17,7 +17,7 @@ staging rows (half.per_sample_gradients -> gad_hgemm_tn_seg); with fp32 activati
 through the flat buffer, as `gradient_features` does.
 
 `journey_latents` / `journey_gradient_features` are Journey-TRAK's validation side (d_trak_grad.py --calculate_gen_grad, reference
-:450-494, :729-731): batched ancestral DDPM trajectories stepped by gad_ddpm_step (csrc/ddpm.hip: one launch per step, variance
+:450-494, :729-731): batched ancestral DDPM trajectories stepped by gad_ddpm_step (csrc/sampler.hip: one launch per step, variance
 noise from in-kernel Philox keyed per sample), and the features of their latents taken as they are through the same _GradStep."""
 from __future__ import annotations
 
@@ -275,8 +275,6 @@ def journey_latents(model, scheduler, n_samples, k_partition, opt_seed=42, batch
     ts = journey_timesteps(k_partition, T)
     K = len(ts)
     stride = T // int(posterior_steps)
-    clip = float(c.clip_sample_range) if c.clip_sample else 0.0
-    ac = scheduler.alphas_cumprod
     ss = model.config.sample_size
     H, W = ss if isinstance(ss, (tuple, list)) else (ss, ss)
     C_in = model.config.in_channels
@@ -295,9 +293,8 @@ def journey_latents(model, scheduler, n_samples, k_partition, opt_seed=42, batch
             for i, t in enumerate(ts[:-1]):
                 tdev.fill_(t)
                 eps = model(slab[i, :n], tdev[:n]).sample.contiguous()
-                prev_t = t - stride
-                ops.ddpm_step_raw(slab[i, :n], eps, seeds, t, ac[t].item(), ac[prev_t].item() if prev_t >= 0 else 1.0, clip,
-                                  c.variance_type, out=slab[i + 1, :n])
+                ops.ddpm_step_raw(slab[i, :n], eps, seeds, t, *scheduler.alpha_pair(t, t - stride), scheduler.clip, c.variance_type,
+                                  out=slab[i + 1, :n])
             out[s0:s0 + n] = slab[:, :n].flip(0).transpose(0, 1).cpu()
     finally:
         model.train(was_training)

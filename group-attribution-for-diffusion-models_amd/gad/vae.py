@@ -37,6 +37,7 @@ import torch
 
 from . import _capi, ops
 from .extractor import Extractor, check_state_dict, file_tag, load_checkpoint
+from .schedulers import randn_tensor
 
 EPS = 1e-6
 # gad_attention_fwd_d512 takes a CU per workgroup of 64 queries (132 KB of LDS), so below one workgroup per CU its time is
@@ -196,11 +197,7 @@ class DiagonalGaussian:
 
     def sample(self, generator=None):
         """mean + std * randn; a CPU generator draws on the host and the noise is moved (diffusers' randn_tensor)"""
-        if generator is not None and generator.device.type == "cpu":
-            noise = torch.randn(self.mean.shape, generator=generator, dtype=self.mean.dtype).to(self.mean.device)
-        else:
-            noise = torch.randn(self.mean.shape, generator=generator, dtype=self.mean.dtype, device=self.mean.device)
-        return self.mean + self.std * noise
+        return self.mean + self.std * randn_tensor(self.mean.shape, generator, self.mean.device, self.mean.dtype)
 
 
 class _Autoencoder(Extractor):

@@ -598,7 +598,7 @@ int64_t gad_jl_project_workspace_bytes(const gad_jl_args* a);
 int gad_jl_project(const gad_jl_args* a, void* stream);
 
 /* ------------------------------------------------------------------------------
- * Ancestral DDPM update with in-kernel variance noise (csrc/ddpm.hip): the scheduler.step of the Journey-TRAK
+ * Ancestral DDPM update with in-kernel variance noise (csrc/sampler.hip): the scheduler.step of the Journey-TRAK
  * trajectory generator (reference src/attributions/methods/d_trak_grad.py:472-479, diffusers DDPMScheduler.step with
  * epsilon prediction).  x, eps, x_prev: B rows of n contiguous floats.  Per element, with cur_alpha = alpha_t / alpha_prev:
  *   x0     = (x - sqrt(1 - alpha_t) eps) / sqrt(alpha_t), clamped to +-clip when clip > 0
@@ -623,7 +623,7 @@ int gad_ddpm_step(const float* x, const float* eps, float* x_prev, int32_t B, in
                   float alpha_t, float alpha_prev, float clip, int32_t variance_type, void* stream);
 
 /* ------------------------------------------------------------------------------
- * One PLMS step of the PNDM sampler (csrc/plms.hip; diffusers PNDMScheduler.step_plms with skip_prk_steps, epsilon
+ * One PLMS step of the PNDM sampler (csrc/sampler.hip; diffusers PNDMScheduler.step_plms with skip_prk_steps, epsilon
  * prediction - what the reference's StableDiffusionPipeline runs, text_to_image/compute_model_behaviors.py:311-326).
  * Every operand is n contiguous floats.  Per element:
  *   e      = eps_u + guidance (eps_c - eps_u)     (eps_c == NULL: e = eps_u, guidance is not read)

@@ -1,4 +1,4 @@
-"""Journey-TRAK: the fused ancestral DDPM step (csrc/ddpm.hip) against gad.DDPMScheduler.step's torch path, and a whole
+"""Journey-TRAK: the fused ancestral DDPM step (csrc/sampler.hip) against gad.DDPMScheduler.step's torch path, and a whole
 journey_latents on the CIFAR U-Net.  One process:
 
   step      ops.ddpm_step_raw (one launch, noise generated in the kernel) against gad.DDPMScheduler.step (about a dozen

@@ -1,4 +1,4 @@
-"""PNDM (PLMS) sampler: the fused guided step (csrc/plms.hip) against the same update written in torch ops and against the
+"""PNDM (PLMS) sampler: the fused guided step (csrc/sampler.hip) against the same update written in torch ops and against the
 guided DDIM step it stands beside.  One process, per shape ([16][4][64][64] and [64][4][32][32] latents, guidance 7.5):
 
   plms      PNDMScheduler's launch in its costliest mode - a guided four-term step that pushes into the ring, in place:
